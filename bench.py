@@ -21,10 +21,19 @@ Workload (config.workload):
       metric's target (">= 2M Gaussians ... >= 120 views/s on 1 x MI355X") is quoted on.
   c2  BASELINE.json configs[1]: 200k Gaussians (50/50 sigma0 mix), 4 views 800x800.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel,
-HIP-event timed on the launch stream in a second pass of the same K steps) and
-`cpu_baseline` (the oracle's C restatement on the host cores, bounded sample, rank 0,
-N=1 only).  Inputs are resident in HBM before the timed region starts.
+Prints ONE JSON line (rank 0) with the contract fields (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  Inputs are resident in HBM before the
+timed region starts.  A plain run sets up, warms up, times the K steps and prints the line;
+everything else is measured only with `--full`: `roofline` (dominant kernel, HIP-event
+timed on the launch stream in a second pass of the same K steps), the `per_view` and
+`images_out` headlines, the collectives' own times (`comm_ms`), `cpu_baseline` (the
+oracle's C restatement on the host cores, bounded sample, rank 0, N=1 only), the PyTorch-CPU
+baseline, `psnr_vs_oracle`, `loss_mean` and `grad_l1`.
+
+    --dump-outputs DIR   after the timed steps, what the timed path computed in its last
+                         step (per-view losses, the Gaussians' gradients on a fixed seeded
+                         sample of rows) as DIR/<name>.npy, for output-by-output comparison
+                         of two builds on identical (seeded) inputs
 """
 from __future__ import annotations
 
@@ -45,6 +54,43 @@ import torch.distributed as dist
 K7_SETTLE_STEPS = 13   # untimed steps in front of --warmup: the K7 choice of a launch shape is made after its 12th launch
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s achievable
 ATOMIC_PEAK_LINES = 21.0e9   # float-atomic 64-byte record lines / s the device sustains (measured: scripts/atomic_probe.hip)
+DUMP_ROWS = 65_536     # --dump-outputs: rows (Gaussians, pixels) of a larger output kept, a fixed seeded sample
+DUMP_LIMIT = 64 * 2**20   # --dump-outputs: bytes written at most
+
+
+def sample_rows(n, k=DUMP_ROWS, seed=0):
+    """Sorted indices of a fixed, seeded sample of k of n rows (all n rows when n <= k)."""
+    if n <= k:
+        return torch.arange(n)
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, float64 where given so and float32 otherwise."""
+    import numpy as np
+
+    res = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        res[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in res.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in res.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] wrote {len(res)} arrays ({total} bytes) to {out_dir}", file=sys.stderr, flush=True)
+
+
+def gaussian_outputs(grads, n_rows):
+    """The per-Gaussian outputs of a step (gradients, leading dimension n_rows) on a fixed seeded sample of rows, plus
+    the sample's row indices (float64: exact)."""
+    idx = sample_rows(n_rows)
+    out = {"gaussian_rows": idx.double()}
+    for name, g in grads.items():
+        if g is not None:
+            out["grad_" + name] = g.detach().reshape(n_rows, -1)[idx.to(g.device)]
+    return out
 
 WORKLOADS = {
     "c4": dict(n=2_000_000, sigma0=(0.00065,), seed=3, views_per_gpu=4, h=800, w=800, deg=3,
@@ -241,16 +287,23 @@ def run_c3step(args, wl, dev, rank, world, use_dist, barrier_fn):
         return el, float(last)
 
     el_f, loss_f = timed(fused_step, args.steps, args.warmup)
-    el_c, loss_c = timed(caller_step, max(1, min(args.steps, 10)), max(1, min(args.warmup, 3)))
+    if args.dump_outputs and rank == 0:     # the last timed step: its loss and the gradients of both Gaussian sets
+        outs = {"loss": torch.tensor([loss_f], dtype=torch.float64)}
+        for tag, leaf_set in (("coarse", lc), ("fine", lf)):
+            rows = leaf_set["centers"].shape[0] * leaf_set["centers"].shape[1]      # (B samples x N Gaussians)
+            outs.update({f"{tag}_{k}": v for k, v in gaussian_outputs({k: p.grad for k, p in leaf_set.items()}, rows).items()})
+        dump_outputs(args.dump_outputs, outs)
     k_c = max(1, min(args.steps, 10))
-    el_c_prebuilt = None
-    if fresh["on"]:         # the same sequence from cameras built once: what the per-call MiniCam costs the caller
+    el_c = loss_c = el_c_prebuilt = None
+    if args.full:           # second headline: the unchanged caller's sequence
+        el_c, loss_c = timed(caller_step, k_c, max(1, min(args.warmup, 3)))
+    if args.full and fresh["on"]:   # the same sequence from cameras built once: what the per-call MiniCam costs the caller
         fresh["on"] = False
         el_c_prebuilt, _ = timed(caller_step, k_c, 2)
         fresh["on"] = True
     kernels = {}
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         L.profile_enable(True)
         L.profile_collect(reset=True)
         for _ in range(min(args.steps, 3)):
@@ -309,7 +362,7 @@ def run_c3step(args, wl, dev, rank, world, use_dist, barrier_fn):
                             note="achieved / frac: the dominant kernel's algorithmic bytes summed over the step's launches "
                                  "(two Gaussian sets, three nodes per sample) over its summed launch time")
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import numpy as np
         from oracle.gdr_oracle import Oracle, Settings
         cores = os.cpu_count() or 1
@@ -334,7 +387,18 @@ def run_c3step(args, wl, dev, rank, world, use_dist, barrier_fn):
                             sample=f"oracle C restatement (OpenMP, {cores} threads), {reps} x fwd+bwd of 1 coarse view {h}x{w}, "
                                    f"{n} Gaussians ({tc:.3f} s each); a render of the fine set costs about the same")
     v_f = renders * args.steps / el_f
-    v_c = renders * k_c / el_c
+    per_view = None
+    if el_c is not None:
+        v_c = renders * k_c / el_c
+        per_view = {"value": round(v_c, 2), "unit": "renders/s", "ms_per_step": round(1e3 * el_c / k_c, 3),
+                    "ms_per_sample": round(1e3 * el_c / k_c / B, 3), "steps": k_c, "of_fused": round(v_c / v_f, 3),
+                    "entry": "the unchanged caller: render_img per view (torch activations, new settings + carrier per call), "
+                             "torch.autograd.functional.vjp + torch.topk, losses on the width-concatenated views, one backward",
+                    "cameras": ("built once (--prebuilt-cams)" if args.prebuilt_cams else
+                                "a MiniCam built on the device in front of every render call (network.py:832,851,970 -> utils.py:22-48)"),
+                    "value_prebuilt_cams": None if el_c_prebuilt is None else round(renders * k_c / el_c_prebuilt, 2),
+                    "ms_per_sample_prebuilt_cams": None if el_c_prebuilt is None else round(1e3 * el_c_prebuilt / k_c / B, 3),
+                    "host_boundary": "compiled (csrc/boundary.cpp)" if L.boundary() is not None else "python + ctypes"}
     return {
         "metric": "renders/sec fwd+bwd @ 512x512, reference train-step sequence", "value": round(v_f, 2), "unit": "renders/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * el_f / args.steps, 3),
@@ -344,15 +408,7 @@ def run_c3step(args, wl, dev, rank, world, use_dist, barrier_fn):
                    "renders_per_sample": 2 * V + VS, "image": [h, w], "sh_degree": deg, "layout": args.layout,
                    "parallelism": f"scene-sharded x{world} (the reference's DDP)", "peak_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2),
                    "entry": "render_views_loss (coarse, fine) + screenspace_absgrad(topk) per sample: 3 rasterizer nodes"},
-        "per_view": {"value": round(v_c, 2), "unit": "renders/s", "ms_per_step": round(1e3 * el_c / k_c, 3),
-                     "ms_per_sample": round(1e3 * el_c / k_c / B, 3), "steps": k_c, "of_fused": round(v_c / v_f, 3),
-                     "entry": "the unchanged caller: render_img per view (torch activations, new settings + carrier per call), "
-                              "torch.autograd.functional.vjp + torch.topk, losses on the width-concatenated views, one backward",
-                     "cameras": ("built once (--prebuilt-cams)" if args.prebuilt_cams else
-                                 "a MiniCam built on the device in front of every render call (network.py:832,851,970 -> utils.py:22-48)"),
-                     "value_prebuilt_cams": None if el_c_prebuilt is None else round(renders * k_c / el_c_prebuilt, 2),
-                     "ms_per_sample_prebuilt_cams": None if el_c_prebuilt is None else round(1e3 * el_c_prebuilt / k_c / B, 3),
-                     "host_boundary": "compiled (csrc/boundary.cpp)" if L.boundary() is not None else "python + ctypes"},
+        "per_view": per_view,
         "loss_fused": loss_f, "loss_per_view": loss_c, "roofline": roofline, "cpu_baseline": cpu_baseline, "kernels": kernels,
         "spread": "same box run-to-run +-0.3 %, box-to-box +-4 % (BASELINE.md section 4)",
         "gc": "Python's cyclic collector disabled inside the timed regions (timeit convention; collected right before)",
@@ -403,7 +459,7 @@ def run_forward_only(args, wl, dev, rank, world, use_dist, barrier_fn):
                 cs = cams[lo:lo + 8]
                 outs = (r_fused.render_views(cs, rays[lo:lo + 8], None, *a) if surfel else r_fused.render_views(cs, None, *a))
                 acc = acc + outs[-1]["image"][0, 0, 0]      # (every frame is consumed, as the video writer does)
-            return acc
+            return outs     # (the last chunk's frames: what --dump-outputs writes)
 
     def caller_step():
         with torch.no_grad():
@@ -420,7 +476,7 @@ def run_forward_only(args, wl, dev, rank, world, use_dist, barrier_fn):
         gc.disable()
         t0 = time.perf_counter()
         for _ in range(k):
-            fn()
+            last = fn()
         barrier_fn()
         el = time.perf_counter() - t0
         gc.enable()
@@ -428,15 +484,24 @@ def run_forward_only(args, wl, dev, rank, world, use_dist, barrier_fn):
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el
+        return el, last
 
-    k = max(1, min(args.steps, 5))
-    el_v = timed(views_step, k, max(1, min(args.warmup, 2)))
-    el_c = timed(caller_step, k, 1)
-    v_v, v_c = V * k * world / el_v, V * k * world / el_c
+    k = args.steps
+    el_v, last_outs = timed(views_step, k, max(1, min(args.warmup, 2)))
+    if args.dump_outputs and rank == 0:     # the maps of the last chunk's views in the last timed step, a seeded pixel sample
+        px = sample_rows(h * w)
+        maps = {f"{key}_last_views": torch.stack([o[key].reshape(h * w, -1)[px.to(dev)] for o in last_outs]) for key in last_outs[0]}
+        dump_outputs(args.dump_outputs, dict(maps, pixel_rows=px.double()))
+    v_v, per_view = V * k * world / el_v, None
+    if args.full:           # second headline: the unchanged caller
+        k_c = max(1, min(args.steps, 5))
+        el_c, _ = timed(caller_step, k_c, 1)
+        v_c = V * k_c * world / el_c
+        per_view = {"value": round(v_c, 2), "unit": "views/s", "ms_per_step": round(1e3 * el_c / k_c, 3), "of_fused": round(v_c / v_v, 3),
+                    "entry": "the unchanged caller: render_img per frame under no_grad (torch activations, one native forward call)"}
     # per-kernel times of the fused leg and the algorithmic bytes of the forward kernels
     kernels, roofline = {}, None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         from generativedensification_amd import rasterizer as R
         from generativedensification_amd import surfel_rasterizer as SR
         with torch.no_grad():
@@ -473,7 +538,7 @@ def run_forward_only(args, wl, dev, rank, world, use_dist, barrier_fn):
                             avg_launch_us=kernels[dom]["avg_us"], path_bytes_step_built=int(built),
                             path_frac_built=round(built / (el_v / k) / 1e9 / HBM_PEAK_GBS, 4), num_rendered_view0=int(d0))
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import numpy as np
         from oracle.gdr_oracle import Oracle, Settings
         from oracle.gsr_oracle import SurfelOracle
@@ -504,9 +569,7 @@ def run_forward_only(args, wl, dev, rank, world, use_dist, barrier_fn):
                    "image": [h, w], "sh_degree": deg, "layout": args.layout, "parallelism": f"replicas x{world}",
                    "entry": "render_views, <= 8 views per K1 launch, activations fused into K1",
                    "peak_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)},
-        "per_view": {"value": round(v_c, 2), "unit": "views/s", "ms_per_step": round(1e3 * el_c / k, 3), "of_fused": round(v_c / v_v, 3),
-                     "entry": "the unchanged caller: render_img per frame under no_grad (torch activations, one native forward call)"},
-        "roofline": roofline, "cpu_baseline": cpu_baseline, "kernels": kernels,
+        "per_view": per_view, "roofline": roofline, "cpu_baseline": cpu_baseline, "kernels": kernels,
         "gc": "Python's cyclic collector disabled inside the timed regions (timeit convention; collected right before)",
     }
 
@@ -579,6 +642,13 @@ def main():
                     help="the unchanged-caller legs (`per_view`, c3step's caller_step, --per-view) render from cameras built once "
                          "instead of building a MiniCam on the device in front of every render call as "
                          "/root/reference/lightning/network.py:832,851,970 do (default: per call, the reference's loop)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline / per-kernel pass, the per_view and images_out "
+                         "headlines, the collectives' own times, the CPU baselines, PSNR vs the oracle, loss_mean / grad_l1 "
+                         "(the --no-* options below switch single parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: a fixed seeded sample of the rows of larger outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
@@ -741,6 +811,7 @@ def main():
         fresh = per_view and not (args.prebuilt_cams or prebuilt_override["on"])
 
         def step():
+            steps_run[0] += 1
             for p in plist:
                 if args.keep_grads and p.grad is not None:
                     p.grad.zero_()
@@ -833,6 +904,7 @@ def main():
             return all_losses
         return step
 
+    steps_run = [0]         # steps executed so far, every leg: the timed region's count is read from it, not from --steps
     comm_events = None      # a list while the collectives are being timed
     pending_box: dict = {}
 
@@ -870,11 +942,13 @@ def main():
         import cProfile
         prof_host = cProfile.Profile()
         prof_host.enable()
+    n_before = steps_run[0]
     t0 = time.perf_counter()
     for _ in range(args.steps):
         last_losses = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    timed_steps = steps_run[0] - n_before
     gc.enable()
     if prof_host is not None:
         import io
@@ -890,18 +964,22 @@ def main():
         dist.all_gather(all_t, mine_t)
         per_rank = [float(x.item()) for x in all_t]
         elapsed = max(per_rank)
-        rank_ms = [round(1e3 * x / args.steps, 3) for x in per_rank]
-    views_per_sec = total_views * args.steps / elapsed
-    ms_per_step = 1e3 * elapsed / args.steps
+        rank_ms = [round(1e3 * x / timed_steps, 3) for x in per_rank]
+    views_per_sec = total_views * timed_steps / elapsed
+    ms_per_step = 1e3 * elapsed / timed_steps
 
     def note(msg):
         if rank == 0:
             print(f"[bench] {msg} (t+{time.perf_counter() - t0:.1f}s)", file=sys.stderr, flush=True)
 
     note(f"timed region done: {views_per_sec:.1f} views/s")
+    # ---- what the last timed step computed: the per-view losses and the Gaussians' gradients (a seeded sample of rows)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(gaussian_outputs({k: p.grad for k, p in params.items()}, n),
+                                             view_losses=last_losses))
     # ---- the collectives on their own (HIP events around each, a short extra pass; inside `value` they are part of the step)
     comm_ms = None
-    if use_dist:
+    if use_dist and args.full:
         comm_events = []
         for _ in range(max(1, min(args.steps, 5))):
             step()
@@ -929,12 +1007,12 @@ def main():
                        note="ms per step on this rank, HIP events on the caller's stream around gather_view_losses / "
                             "allreduce_gaussian_grads (packing included); rank 0")
         comm_events = None
-    # ---- D (num_rendered) per view, measured ----------------------------------------
+    # ---- D (num_rendered) per view, measured (--full: one more forward per view) ---------------------
     from generativedensification_amd import rasterizer as R
     from generativedensification_amd import surfel_rasterizer as SR
     d_views, pair_views, class_entries = [], [], [0, 0, 0]
     with torch.no_grad():
-        for cam in cams:
+        for cam in (cams if args.full else ()):
             rs = renderer.set_rasterizer(cam, device=dev).raster_settings
             e = torch.empty(0, device=dev)
             fr = (SR if surfel else R).forward_raw(params["centers"].detach(), params["shs"].detach(), e,
@@ -955,7 +1033,7 @@ def main():
             except Exception:
                 pass
             del st, fr
-    d_mean = sum(d_views) / len(d_views)
+    d_mean = sum(d_views) / max(1, len(d_views))
     tiles = ((w + 15) // 16) * ((h + 15) // 16)
     m = (deg + 1) ** 2
     alg = (surfel_algorithmic_bytes if surfel else algorithmic_bytes)(n, d_mean, h * w, m, tiles, min(vpg, 8))
@@ -984,7 +1062,7 @@ def main():
         L.profile_enable(False)
         return prof
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         prof = profiled(step, args.steps)
         # PMC tables (rocprofv3 --pmc passes, scripts/gpu_pmc.sh -> scripts/make_pmc_traffic.py) hold for ONE scene: the
         # figures are used only when the table's recorded scene is the one being run; otherwise traffic is null and no
@@ -1142,7 +1220,7 @@ def main():
     # all the graphs.  `value` above is the fused multi-view entry a modified caller can use; this is what the reference's
     # files get as they are.
     per_view = None
-    if not (args.per_view or args.backward_per_view or args.no_per_view_leg):
+    if args.full and not (args.per_view or args.backward_per_view or args.no_per_view_leg):
         pv_step = make_step(True, True)
         for _ in range(max(1, min(args.warmup, 13))):     # (13: the K7 choice of this launch shape settles after 12 launches)
             pv_step()
@@ -1198,7 +1276,7 @@ def main():
     # what a caller gets that switches its per-view loop to ONE render_views call and keeps its own loss: images (and depth /
     # alpha maps) written, torch ops for the loss, dL/dimage tensors read by K7.
     images_out = None
-    if not (args.per_view or args.backward_per_view or args.no_per_view_leg or args.torch_loss or args.image_loss):
+    if args.full and not (args.per_view or args.backward_per_view or args.no_per_view_leg or args.torch_loss or args.image_loss):
         io_step = make_step(False, False, torch_loss=True)
         for _ in range(max(1, min(args.warmup, 13)) if args.no_settle else K7_SETTLE_STEPS):
             io_step()
@@ -1225,7 +1303,7 @@ def main():
     # ---- CPU baseline: oracle (C restatement, OpenMP) on a bounded sample ------------------
     cpu_baseline = None
     psnr_vs_oracle = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import numpy as np
         from oracle.gdr_oracle import Oracle, Settings
         from oracle.gsr_oracle import SurfelOracle
@@ -1316,7 +1394,7 @@ def main():
     # the cost per view is linear in the number of Gaussians at fixed tile occupancy, so the rate is scaled by n_s / n)
     note("C-oracle baseline done")
     cpu_baseline_torch = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not surfel and args.workload != "c3":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not surfel and args.workload != "c3":
         import subprocess
         thr = min(os.cpu_count() or 1, 16)   # torch's intra-op pool degrades on small per-tile tensors beyond this
         cmd = [sys.executable, os.path.join(ROOT, "scripts", "torch_cpu_baseline.py"), "--n", str(n), "--seed", str(wl["seed"]),
@@ -1337,12 +1415,12 @@ def main():
         out = {
             "metric": "views/sec fwd+bwd @ 800x800", "value": round(views_per_sec, 2), "unit": "views/s",
             "n_gpus": world, "world_size": dist.get_world_size() if use_dist else 1,
-            "dist_backend": (dist.get_backend() if use_dist else None), "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "dist_backend": (dist.get_backend() if use_dist else None), "steps": args.steps, "timed_steps": timed_steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "ms_per_step_ranks": rank_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic (seeded random Gaussians with the decoder's statistics, random targets)",
             "config": {"workload": f"{args.workload}: {wl['desc']}", "n_gaussians": n, "layout": args.layout, "order": args.order,
                        "views_per_gpu": vpg, "image": [h, w], "sh_degree": deg,
-                       "num_rendered_per_view": int(d_mean), "parallelism": f"view-sharded x{world}",
+                       "num_rendered_per_view": int(d_mean) if d_views else None, "parallelism": f"view-sharded x{world}",
                        "grad_allreduce": bool(args.grad_allreduce),
                        "peak_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2),
                        "entry": ("renderer_2dgs.render_views (all views of the shard, one node)" if surfel and not (args.per_view or args.backward_per_view or args.torch_loss or args.unfused)
@@ -1366,10 +1444,11 @@ def main():
             "gc": "Python's cyclic collector disabled inside the timed regions (timeit convention; collected right before)",
             "cpu_baseline": cpu_baseline, "cpu_baseline_torch": cpu_baseline_torch,
             "psnr_vs_oracle": psnr_vs_oracle, "kernels": kernels,
-            "loss_mean": float(last_losses.mean()),
+            "loss_mean": float(last_losses.mean()) if args.full else None,
             # L1 norms of the Gaussians' gradients after the last step (with --grad-allreduce: of the sum over all ranks'
             # views) — lets a 2-rank run be compared with one rank rendering the same views (tests/test_gpu_multirank.py)
-            "grad_l1": {k: (float(p.grad.double().abs().sum()) if p.grad is not None else None) for k, p in params.items()},
+            "grad_l1": ({k: (float(p.grad.double().abs().sum()) if p.grad is not None else None) for k, p in params.items()}
+                        if args.full else None),
         }
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if use_dist:

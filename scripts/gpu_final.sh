@@ -22,7 +22,7 @@ done
 python scripts/make_pmc_traffic.py $O/${TAG} && cp $O/pmc_traffic.json profiles/pmc_traffic.json
 echo "--- K7 stall breakdown at the reference's own scale (pairs kernel pinned), round-4 verdict next #4"
 for wl in c2 c3 c4; do
-  timeout 600 python bench.py --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --no-per-view-leg > $O/k7line_$wl.json 2>/dev/null
+  timeout 600 python bench.py --workload $wl --steps 10 --warmup 3 --full --no-cpu-baseline --no-per-view-leg > $O/k7line_$wl.json 2>/dev/null
   python scripts/k7_stalls.py $O/${TAG}_${wl}_pmc_summary.json $O/k7line_$wl.json $O/${TAG}_k7_stalls_$wl.json | cut -c1-400
 done
 python scripts/binning_stalls.py $O/${TAG}_c4_pmc_summary.json $O/k7line_c4.json $O/${TAG}_binning_stalls.json | cut -c1-600
@@ -31,7 +31,7 @@ for st in 1 2 4 8 16 32 3 7 23; do [ -f generativedensification_amd/lib/variants
 bash scripts/gpu_k7_budget.sh > $O/k7_budget.log 2>&1; cp gpurun_out/k7_budget/k7_budget.json $O/${TAG}_k7_budget.json 2>/dev/null; tail -3 $O/k7_budget.log | cut -c1-300
 for u in valu_rate valu_select; do P=generativedensification_amd/lib/$u; [ -x $P ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 scripts/ubench/$u.hip -o $P 2>/dev/null; timeout 120 $P > $O/${TAG}_$u.txt 2>&1; done
 for k in 20 21 22 23 24 25 26 27; do timeout 15 generativedensification_amd/lib/valu_select $k >> $O/${TAG}_valu_select.txt 2>&1; done
-b() { name=$1; shift; timeout 1200 python bench.py "$@" > $O/${TAG}_bench_$name.json 2> $O/bench_$name.err || tail -3 $O/bench_$name.err
+b() { name=$1; shift; timeout 1200 python bench.py --full "$@" > $O/${TAG}_bench_$name.json 2> $O/bench_$name.err || tail -3 $O/bench_$name.err
   python - <<PY
 import json
 try:
@@ -81,18 +81,18 @@ echo "--- abs-grad entry + device top-k"
 python scripts/absgrad_bench.py 2>/dev/null | tee $O/${TAG}_absgrad.txt
 echo "--- size sweep (every frac must stay <= 1; traffic null off the recorded scene)"
 for n in 500000 2000000 8000000 32000000; do
-  timeout 900 python bench.py --n $n --steps 20 --warmup 3 --no-cpu-baseline --no-per-view-leg > $O/n$n.json 2> $O/n$n.err || { echo "N=$n FAILED"; tail -3 $O/n$n.err; continue; }
+  timeout 900 python bench.py --n $n --steps 20 --warmup 3 --full --no-cpu-baseline --no-per-view-leg > $O/n$n.json 2> $O/n$n.err || { echo "N=$n FAILED"; tail -3 $O/n$n.err; continue; }
   python -c "
 import json; d=json.load(open('$O/n$n.json')); r=d['roofline'] or {}
 fr=[k.get('frac',0) for k in d['kernels'].values()]+[k.get('frac_serial',0) or 0 for k in d['kernels'].values()]
 print(json.dumps(dict(n=$n, views_per_s=d['value'], ms_per_step=d['ms_per_step'], D=d['config']['num_rendered_per_view'], path_frac=r.get('path_frac'), path_frac_measured=r.get('path_frac_measured'), traffic=r.get('traffic'), max_kernel_frac=max(fr), mem_gb=d['config'].get('peak_mem_gb'))))" | tee -a $O/${TAG}_size_sweep.json
 done
 echo "--- RCCL, one rank, collectives forced: plain / K9 writing into the packed buffer (gradient sinks) / the same with the collectives asynchronous / gradients kept"
-timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-per-view-leg 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank_plain.json | cut -c1-120
-timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-per-view-leg --force-dist --grad-allreduce 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank.json | cut -c1-200
-timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-per-view-leg --force-dist --grad-allreduce --separate-loss-gather 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank_separate_loss_gather.json | cut -c1-200
-timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-per-view-leg --force-dist --grad-allreduce --overlap-comm 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank_overlap.json | cut -c1-200
-timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-roofline --no-per-view-leg --force-dist --grad-allreduce --keep-grads 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank_keepgrads.json | cut -c1-200
+timeout 600 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-roofline --no-per-view-leg 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank_plain.json | cut -c1-120
+timeout 600 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-roofline --no-per-view-leg --force-dist --grad-allreduce 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank.json | cut -c1-200
+timeout 600 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-roofline --no-per-view-leg --force-dist --grad-allreduce --separate-loss-gather 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank_separate_loss_gather.json | cut -c1-200
+timeout 600 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-roofline --no-per-view-leg --force-dist --grad-allreduce --overlap-comm 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank_overlap.json | cut -c1-200
+timeout 600 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-roofline --no-per-view-leg --force-dist --grad-allreduce --keep-grads 2>/dev/null | tail -1 | tee $O/${TAG}_bench_rccl_1rank_keepgrads.json | cut -c1-200
 echo "--- the reference's per-sample sequence through the unchanged caller: phases, forward reuse on / off, kernel timeline"
 python scripts/c3step_phases.py 2>/dev/null | tee $O/${TAG}_c3step_phases.txt | grep -E "^---|sum|unsynchronised"
 python scripts/c3step_phases.py --fresh-cams 2>/dev/null | tee -a $O/${TAG}_c3step_phases.txt | grep -E "^---|sum|unsynchronised"
@@ -102,5 +102,5 @@ echo "--- 2DGS parity statistics at other absolute floors (tests/util.py assert_
 GDR_TEST_STATS=1 timeout 1200 python -m pytest tests/test_gpu_oracle_fullsize.py tests/test_gpu_surfel.py -q -rP -k "surfel" 2>&1 | grep -E "^\[|passed|failed" | cut -c1-200 > $O/${TAG}_surfel_stats.txt; tail -1 $O/${TAG}_surfel_stats.txt
 bash scripts/gpu_timeline.sh c2 --no-per-view-leg > /dev/null 2>&1; cp gpurun_out/timeline_c2.txt $O/${TAG}_timeline_c2.txt; grep "^step [45]" $O/${TAG}_timeline_c2.txt
 echo "--- 2 and 8 ranks on one GPU (gloo)"
-timeout 600 python bench.py --gpus 2 --steps 3 --warmup 1 --workload c2 --single-device --no-roofline --no-per-view-leg 2>/dev/null | tail -1 | tee $O/${TAG}_bench_2ranks_c2.json | cut -c1-260
-timeout 900 python bench.py --gpus 8 --steps 3 --warmup 1 --workload c2 --single-device --no-roofline --no-per-view-leg --no-cpu-baseline 2>/dev/null | tail -1 | tee $O/${TAG}_bench_8ranks_c2.json | cut -c1-360
+timeout 600 python bench.py --gpus 2 --steps 3 --warmup 1 --workload c2 --single-device --full --no-roofline --no-per-view-leg 2>/dev/null | tail -1 | tee $O/${TAG}_bench_2ranks_c2.json | cut -c1-260
+timeout 900 python bench.py --gpus 8 --steps 3 --warmup 1 --workload c2 --single-device --full --no-roofline --no-per-view-leg --no-cpu-baseline 2>/dev/null | tail -1 | tee $O/${TAG}_bench_8ranks_c2.json | cut -c1-360

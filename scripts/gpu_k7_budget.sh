@@ -11,7 +11,7 @@ VARIANTS=${VARIANTS:-"release k7stub1 k7stub2 k7stub4 k7stub8 k7stub16 k7stub32 
 WORKLOADS=${WORKLOADS:-"c4 c3 c2"}
 PMC_WORKLOADS=${PMC_WORKLOADS:-"c4 c3"}
 export GDR_ALLOW_EXPERIMENTAL_LIB=1 GDR_K7_PAIRS=0
-ARGS="--steps 10 --warmup 4 --no-settle --no-cpu-baseline --no-per-view-leg"
+ARGS="--steps 10 --warmup 4 --no-settle --full --no-cpu-baseline --no-per-view-leg"
 for v in $VARIANTS; do
   if [ $v = release ]; then unset GDR_LIB_PATH; else export GDR_LIB_PATH=$R/generativedensification_amd/lib/variants/libgdr_hip_$v.so; [ -f $GDR_LIB_PATH ] || { echo "missing $GDR_LIB_PATH"; continue; }; fi
   for wl in $WORKLOADS; do

@@ -15,7 +15,7 @@ for wl in c4 c2; do for n in 1 2 4 8; do
     tag=$(echo "$mode" | tr -d ' -'); tag=${tag:-render}
     if [ $n -eq 1 ]; then cmd="python bench.py"; else
       cmd="python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29533 bench.py"; fi
-    timeout 900 $cmd --gpus $n --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --no-per-view-leg $mode \
+    timeout 900 $cmd --gpus $n --workload $wl --steps 20 --warmup 5 --full --no-cpu-baseline --no-per-view-leg $mode \
       > $OUT/scale_${wl}_${n}_${tag}.json 2> $OUT/scale_${wl}_${n}_${tag}.err
     python - <<PY
 import json

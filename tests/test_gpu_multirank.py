@@ -127,7 +127,7 @@ def test_bench_two_ranks_with_grad_allreduce_equal_one_rank_with_all_views():
     gradient L1 norms equal up to the order of fp32 sums; the collectives' own times are in the line (`comm_ms`); the
     --keep-grads variant (gradients accumulated into the persistent packed buffer) gives the same sums."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    common = ["--workload", "c2", "--n", "40000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-roofline",
+    common = ["--workload", "c2", "--n", "40000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-roofline",
               "--no-per-view-leg"]
 
     def run(extra):
@@ -168,7 +168,7 @@ def test_bench_line_contract_on_one_gpu():
     that the oracle legs take seconds."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--n", "20000", "--steps", "3",
-                        "--warmup", "1"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout           # exactly ONE line on stdout
@@ -194,3 +194,40 @@ def test_bench_line_contract_on_one_gpu():
     assert out["psnr_vs_oracle"]["psnr_db"] > 60 and out["psnr_vs_oracle"]["max_abs_rgb"] < 5e-3   # "PSNR vs ref" of the metric
     ct = out["cpu_baseline_torch"]
     assert ct["kind"] == "port" and (ct["value"] is None or ct["value"] > 0)
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the contract fields and nothing it had to measure
+    beyond them; with --dump-outputs it writes the last timed step's losses and gradients (float32 / float64, 64 MB at
+    most), and two runs on the same arguments compute the same losses and gradients from the same seeded inputs."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--n", "20000", "--steps", "4",
+                            "--warmup", "1", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        return json.loads(lines[0])
+    out = run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 4 and out["value"] > 0 and out["ms_per_step"] > 0 and out["dtype"] == "f32"
+    assert out["timed_steps"] == 4      # steps the timed region executed, counted inside the step itself
+    assert abs(out["value"] - 4 * 1e3 / out["ms_per_step"]) <= 1e-2 * out["value"]    # 4 views per step
+    assert out["roofline"] is None and out["per_view"] is None and out["cpu_baseline"] is None and out["kernels"] == {}
+    files = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert {"view_losses.npy", "gaussian_rows.npy", "grad_centers.npy", "grad_shs.npy", "grad_opacity.npy",
+            "grad_scales.npy", "grad_rotations.npy"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 2**20
+    assert files["view_losses.npy"].shape == (4,) and files["grad_centers.npy"].shape == (20_000, 3)
+    assert np.isfinite(files["grad_shs.npy"]).all() and np.abs(files["grad_centers.npy"]).sum() > 0
+    run(tmp_path / "b")
+    again = {f.name: np.load(f) for f in (tmp_path / "b").iterdir()}
+    assert set(again) == set(files)
+    np.testing.assert_array_equal(again["gaussian_rows.npy"], files["gaussian_rows.npy"])
+    np.testing.assert_allclose(again["view_losses.npy"], files["view_losses.npy"], rtol=1e-5)
+    for name, a in files.items():       # gradients: equal up to the order of K7's float atomics
+        if name.startswith("grad_"):
+            assert np.linalg.norm(again[name] - a) <= 1e-4 * np.linalg.norm(a), name
