@@ -127,6 +127,15 @@ class GsrGradOutputs(C.Structure):
 
 GSR_REC_FLOATS, GSR_GRAD_FLOATS = 24, 32
 
+GDR_SSIM_MAX_WIN, GDR_SSIM_MAX_LEVELS = 15, 8
+GDR_SSIM_PLAIN, GDR_SSIM_NONNEG, GDR_SSIM_MS = 0, 1, 2
+
+
+class GdrSsimArgs(C.Structure):   # include/gdr.h gdr_ssim_args
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("win_size", C.c_int32),
+                ("levels", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32), ("C1", C.c_float), ("C2", C.c_float),
+                ("win", C.c_float * GDR_SSIM_MAX_WIN), ("weights", C.c_float * GDR_SSIM_MAX_LEVELS)]
+
 # every symbol include/gdr.h and include/gsr.h declare, with its prototype
 _PROTOS = {
     "gdr_abi_version": (C.c_int, []),
@@ -224,6 +233,13 @@ _PROTOS = {
                                         C.c_float, C.c_void_p, C.c_void_p]),
     "gdr_view_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_ssim_workspace_bytes": (C.c_size_t, [C.POINTER(GdrSsimArgs)]),
+    "gdr_ssim_scratch_bytes": (C.c_size_t, [C.POINTER(GdrSsimArgs), C.c_int32]),
+    "gdr_ssim_forward": (C.c_int, [C.POINTER(GdrSsimArgs), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_ssim_backward": (C.c_int, [C.POINTER(GdrSsimArgs), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                    C.c_void_p, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

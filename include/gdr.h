@@ -543,6 +543,36 @@ int gdr_view_loss_backward(const float* color, const float* target, int32_t H, i
                            float w_alpha, const float* g, float* dL_dcolor, float* dL_ddepth, float* dL_dalpha,
                            void* stream);
 
+/* ---- SSIM / MS-SSIM (csrc/ssim.hip; added in v17, backward-compatible) -------------------------------------------------
+ * The image-similarity half of the reference's training loss MSE + 0.5 (1 - MS-SSIM) (lightning/loss.py) and the SSIM of
+ * its evaluation, with the semantics of pytorch_msssim 1.x (restated in the header of csrc/ssim.hip).  X, Y: (B, C, H, W)
+ * fp32 read through element strides (b, c, h, w) — a permuted NHWC view is read in place.  out: B*C device floats, the
+ * per-(batch, channel) value (ssim, relu(ssim) or the MS-SSIM product).  win: the normalised 1-D window (win_size odd,
+ * <= GDR_SSIM_MAX_WIN); weights: one per level (GDR_SSIM_MS).  C1 = (K1 data_range)^2, C2 = (K2 data_range)^2.
+ * workspace (gdr_ssim_workspace_bytes, 256-byte aligned) is written by forward and read by backward of the same arguments
+ * (pooled pyramid, per-block partial sums, per-level coefficients).  backward: grad_out = B*C device floats (d loss / d out);
+ * dX (and dY unless NULL) written through their own strides; scratch: gdr_ssim_scratch_bytes(a, dY != NULL).  No host
+ * synchronisation; sizes of 0 from the _bytes queries mean the arguments are refused (gdr_last_error after the call). */
+#define GDR_SSIM_MAX_WIN 15
+#define GDR_SSIM_MAX_LEVELS 8
+#define GDR_SSIM_PLAIN 0    /* ssim, levels = 1 */
+#define GDR_SSIM_NONNEG 1   /* relu(ssim), levels = 1 */
+#define GDR_SSIM_MS 2       /* ms_ssim, levels = 1..GDR_SSIM_MAX_LEVELS */
+typedef struct gdr_ssim_args {
+    int32_t B, C, H, W;
+    int32_t win_size, levels, mode, reserved;
+    float C1, C2;
+    float win[GDR_SSIM_MAX_WIN];
+    float weights[GDR_SSIM_MAX_LEVELS];
+} gdr_ssim_args;
+size_t gdr_ssim_workspace_bytes(const gdr_ssim_args* a);
+size_t gdr_ssim_scratch_bytes(const gdr_ssim_args* a, int32_t want_dy);
+int gdr_ssim_forward(const gdr_ssim_args* a, const float* X, const int64_t* x_strides, const float* Y,
+                     const int64_t* y_strides, void* workspace, float* out, void* stream);
+int gdr_ssim_backward(const gdr_ssim_args* a, const float* X, const int64_t* x_strides, const float* Y,
+                      const int64_t* y_strides, const void* workspace, const float* grad_out, float* dX,
+                      const int64_t* dx_strides, float* dY, const int64_t* dy_strides, void* scratch, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
