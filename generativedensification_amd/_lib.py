@@ -136,6 +136,19 @@ class GdrSsimArgs(C.Structure):   # include/gdr.h gdr_ssim_args
                 ("levels", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32), ("C1", C.c_float), ("C2", C.c_float),
                 ("win", C.c_float * GDR_SSIM_MAX_WIN), ("weights", C.c_float * GDR_SSIM_MAX_LEVELS)]
 
+GDR_TSDF_R = 16
+
+
+class GdrTsdfView(C.Structure):   # include/gdr.h gdr_tsdf_view
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("E", C.c_float * 12),
+                ("c2w", C.c_float * 12)]
+
+
+class GdrTsdfArgs(C.Structure):   # include/gdr.h gdr_tsdf_args
+    _fields_ = [("V", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("stride", C.c_int32), ("words", C.c_int32),
+                ("n_blocks", C.c_int32), ("voxel", C.c_float), ("trunc", C.c_float), ("lo", C.c_int32 * 3),
+                ("dims", C.c_int32 * 3)]
+
 # every symbol include/gdr.h and include/gsr.h declare, with its prototype
 _PROTOS = {
     "gdr_abi_version": (C.c_int, []),
@@ -240,6 +253,15 @@ _PROTOS = {
     "gdr_ssim_backward": (C.c_int, [C.POINTER(GdrSsimArgs), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
                                     C.c_void_p, C.c_void_p]),
+    "gdr_tsdf_scan_bytes": (C.c_size_t, [C.c_int64]),
+    "gdr_tsdf_stage": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                 C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_tsdf_bounds": (C.c_int, [C.POINTER(GdrTsdfArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_tsdf_allocate": (C.c_int, [C.POINTER(GdrTsdfArgs)] + [C.c_void_p] * 7),
+    "gdr_tsdf_integrate": (C.c_int, [C.POINTER(GdrTsdfArgs)] + [C.c_void_p] * 8),
+    "gdr_tsdf_mc_count": (C.c_int, [C.POINTER(GdrTsdfArgs)] + [C.c_void_p] * 9),
+    "gdr_tsdf_mc_emit": (C.c_int, [C.POINTER(GdrTsdfArgs)] + [C.c_void_p] * 11),
+    "gdr_tsdf_clusters": (C.c_int, [C.c_int32] + [C.c_void_p] * 8),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

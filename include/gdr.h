@@ -573,6 +573,53 @@ int gdr_ssim_backward(const gdr_ssim_args* a, const float* X, const int64_t* x_s
                       const int64_t* y_strides, const void* workspace, const float* grad_out, float* dX,
                       const int64_t* dx_strides, float* dY, const int64_t* dy_strides, void* scratch, void* stream);
 
+/* ---- TSDF fusion and marching-cubes mesh extraction (csrc/tsdf.hip; added in v17, backward-compatible) ------------------
+ * The GPU path of the reference's mesh extraction (Open3D ScalableTSDFVolume semantics, restated in the header of
+ * csrc/tsdf.hip).  Views are staged one by one (gdr_tsdf_stage: sanitised f32 depth and packed 0x00BBGGRR colour, H x W
+ * each; the caller stacks V of them into (V, H, W) arrays), then fused and extracted in phases whose outputs size the next
+ * phase's buffers (the caller reads back: the 6-int bbox; cell_scan[cells] = n_blocks; vcount[n] and tcount[n] = the vertex
+ * and triangle totals, n = n_blocks * GDR_TSDF_R^3):
+ *   gdr_tsdf_bounds     bbox = {min bx, by, bz, max bx, by, bz} of the blocks touched by the sampled pixels of all views
+ *   gdr_tsdf_allocate   (lo, dims = the block grid, set in args) per-cell view masks (cells * words), cell_block = the
+ *                       allocated block's index in (bz, by, bx) order or -1; cell_scan: cells + 1 uint32
+ *   gdr_tsdf_integrate  (n_blocks set) blocks = n_blocks x int4 (bx, by, bz, cell); vol = 5 planes of n_blocks * R^3 fp32
+ *                       (tsdf, weight, r, g, b)
+ *   gdr_tsdf_mc_count   cube_case (int16), vflags (uint8), vcount / tcount (n + 1 uint32) -> exclusive offsets and totals
+ *   gdr_tsdf_mc_emit    vertices / colors (V x 3 fp32), triangles (F x 3 int32) in the canonical order
+ *   gdr_tsdf_clusters   keys / tri_of: the 3F edge keys min(a,b) * V + max(a,b) of the triangles, sorted (stable), and the
+ *                       triangle of each; label (F) = cluster rank (clusters numbered by their smallest triangle), counts
+ *                       (F, first root_rank[F] used); parent (F), root_rank (F + 1) are scratch
+ * scratch: gdr_tsdf_scan_bytes(the largest scanned length: cells, n or F).  Every launch on the caller's stream; nothing here
+ * synchronises with the host. */
+#define GDR_TSDF_R 16
+typedef struct gdr_tsdf_view {
+    float fx, fy, cx, cy;
+    float E[12];      /* world-to-camera, rows 0..2 of the 4x4 extrinsic (f32) */
+    float c2w[12];    /* camera-to-world: rows 0..2 of inverse(E) computed in f64, cast to f32 */
+} gdr_tsdf_view;
+typedef struct gdr_tsdf_args {
+    int32_t V, H, W, stride;     /* views, image size, depth sampling stride of the allocation */
+    int32_t words, n_blocks;     /* words = ceil(V / 32); n_blocks from gdr_tsdf_allocate */
+    float voxel, trunc;          /* voxel length, sdf truncation */
+    int32_t lo[3], dims[3];      /* block grid origin and extent (from the bbox) */
+} gdr_tsdf_args;
+size_t gdr_tsdf_scan_bytes(int64_t n);
+int gdr_tsdf_stage(int32_t H, int32_t W, const float* depth, const int64_t* depth_strides, const void* rgb,
+                   const int64_t* rgb_strides, int32_t rgb_u8, float depth_trunc, float* depth_out, uint32_t* rgb_out,
+                   void* stream);
+int gdr_tsdf_bounds(const gdr_tsdf_args* a, const gdr_tsdf_view* views, const float* depth, int32_t* bbox, void* stream);
+int gdr_tsdf_allocate(const gdr_tsdf_args* a, const gdr_tsdf_view* views, const float* depth, uint32_t* cell_mask,
+                      int32_t* cell_block, uint32_t* cell_scan, void* scratch, void* stream);
+int gdr_tsdf_integrate(const gdr_tsdf_args* a, const gdr_tsdf_view* views, const float* depth, const uint32_t* rgb,
+                       const uint32_t* cell_mask, const int32_t* cell_block, int32_t* blocks, float* vol, void* stream);
+int gdr_tsdf_mc_count(const gdr_tsdf_args* a, const int32_t* cell_block, const int32_t* blocks, const float* vol,
+                      int16_t* cube_case, uint8_t* vflags, uint32_t* vcount, uint32_t* tcount, void* scratch, void* stream);
+int gdr_tsdf_mc_emit(const gdr_tsdf_args* a, const int32_t* cell_block, const int32_t* blocks, const float* vol,
+                     const int16_t* cube_case, const uint8_t* vflags, const uint32_t* voff, const uint32_t* toff,
+                     float* vertices, float* colors, int32_t* triangles, void* stream);
+int gdr_tsdf_clusters(int32_t F, const int64_t* keys, const int64_t* tri_of, int32_t* parent, uint32_t* root_rank,
+                      int32_t* label, int32_t* counts, void* scratch, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
