@@ -5,7 +5,8 @@
 // Specification (Open3D's published algorithm restated; parity with Open3D is unpinned).  All arithmetic is fp32 in the order
 // written; the file is built with -ffp-contract=off so that tests/tsdf_ref.py (the numpy restatement) is matched bit for bit.
 //   depth        D(v, u) := 0 where not finite, <= 0 or > depth_trunc (the caller's alpha mask also zeroes it).  Colour is
-//                uint8, floor(rgb * 255) for float input (np.asarray(rgb * 255, dtype=uint8)).
+//                uint8; float input is staged as p = rgb * 255 in fp32, truncated toward zero, then clipped to 0..255, NaN
+//                giving 0 (floor(rgb * 255) on [0, 1]; +-inf, values above 1 and negatives saturate).
 //   allocation   pixels with u % S == 0, v % S == 0 and d > 0: q = ((u - cx) d / fx, (v - cy) d / fy, d), p = c2w q (c2w = the
 //                inverse of E in f64, cast to f32 by the host).  Every block b with floor((p - trunc) / L) <= b <=
 //                floor((p + trunc) / L) per axis (L = R voxel) is touched by the view.  Blocks are kept in (bz, by, bx) order.

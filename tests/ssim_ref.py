@@ -48,25 +48,50 @@ def ssim_terms(X, Y, g, C1, C2):
     return ssim_map.flatten(2).mean(-1), cs_map.flatten(2).mean(-1)
 
 
-def ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, K=(0.01, 0.03), nonnegative_ssim=False):
+def _window(win_size, win_sigma, win):
+    """The 1-D taps: the Gaussian, or a user `win` given as pytorch_msssim takes it, a (C, 1, 1, k) tensor of identical rows
+    (or the 1-D taps themselves).  blur() applies taps g[t] to x[i + t], a correlation, along H and then along W: exactly
+    what F.conv2d does with that tensor (conv2d does not flip its kernel), so an asymmetric window is not mirrored."""
+    if win is None:
+        return gauss_window(win_size, win_sigma)
+    win = torch.as_tensor(win)
+    rows = win.reshape(-1, win.shape[-1])
+    assert bool((rows == rows[0]).all())
+    return rows[0]
+
+
+def ssim_planes(X, Y, data_range=255, win_size=11, win_sigma=1.5, win=None, K=(0.01, 0.03), nonnegative_ssim=False):
+    """(B, C) per-plane SSIM: what the kernels return before the host-side mean."""
     K1, K2 = K
-    s, _ = ssim_terms(X, Y, gauss_window(win_size, win_sigma), (K1 * data_range) ** 2, (K2 * data_range) ** 2)
-    if nonnegative_ssim:
-        s = torch.relu(s)
+    s, _ = ssim_terms(X, Y, _window(win_size, win_sigma, win), (K1 * data_range) ** 2, (K2 * data_range) ** 2)
+    return torch.relu(s) if nonnegative_ssim else s
+
+
+def ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, win=None, K=(0.01, 0.03),
+         nonnegative_ssim=False):
+    s = ssim_planes(X, Y, data_range, win_size, win_sigma, win, K, nonnegative_ssim)
     return s.mean() if size_average else s.mean(1)
 
 
-def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, weights=None, K=(0.01, 0.03)):
+def ms_ssim_planes(X, Y, data_range=255, win_size=11, win_sigma=1.5, win=None, weights=None, K=(0.01, 0.03), pool=None):
+    """(B, C) per-plane MS-SSIM.  `pool` replaces pool2 (the CPU tests pass mutants of it)."""
     K1, K2 = K
-    g = gauss_window(win_size, win_sigma)
-    w = torch.tensor(MS_WEIGHTS if weights is None else weights, dtype=X.dtype, device=X.device)
-    assert min(X.shape[-2:]) > (win_size - 1) * 2 ** (w.numel() - 1)
+    pool = pool2 if pool is None else pool
+    g = _window(win_size, win_sigma, win)
+    weights = MS_WEIGHTS if weights is None else weights
+    w = (weights.to(dtype=X.dtype, device=X.device) if torch.is_tensor(weights)
+         else torch.tensor(weights, dtype=X.dtype, device=X.device))
+    assert min(X.shape[-2:]) > (g.numel() - 1) * 2 ** (w.numel() - 1)
     vals = []
     for lvl in range(w.numel()):
         s, cs = ssim_terms(X, Y, g, (K1 * data_range) ** 2, (K2 * data_range) ** 2)
         if lvl < w.numel() - 1:
             vals.append(torch.relu(cs))
-            X, Y = pool2(X), pool2(Y)
+            X, Y = pool(X), pool(Y)
     vals.append(torch.relu(s))
-    v = torch.prod(torch.stack(vals) ** w.view(-1, 1, 1), dim=0)
+    return torch.prod(torch.stack(vals) ** w.view(-1, 1, 1), dim=0)
+
+
+def ms_ssim(X, Y, data_range=255, size_average=True, win_size=11, win_sigma=1.5, win=None, weights=None, K=(0.01, 0.03)):
+    v = ms_ssim_planes(X, Y, data_range, win_size, win_sigma, win, weights, K)
     return v.mean() if size_average else v.mean(1)

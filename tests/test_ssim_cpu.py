@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import ssim_cases as SC
 import ssim_ref as R
 
 
@@ -135,6 +136,17 @@ def test_argument_errors():
     win = torch.rand(3, 1, 1, 11)
     with pytest.raises(ValueError):     # per-channel-different window
         ssim(X, X, win=win)
+    # a 1-tap window and a single level are supported: the host checks pass them on (here to the refusal of CPU tensors)
+    tiny = torch.rand(1, 1, 4, 3)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ms_ssim(tiny, tiny, win_size=1, weights=(0.3, 0.5, 0.4))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ms_ssim(torch.rand(1, 1, 11, 11), torch.rand(1, 1, 11, 11), weights=(1.7,))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ssim(tiny, tiny, win_size=1)
+    for bad in ((), (0.1,) * 9):        # 1..GDR_SSIM_MAX_LEVELS weights
+        with pytest.raises(ValueError):
+            ms_ssim(X, X, weights=bad)
 
 
 def test_library_exports_the_ssim_entry_points_and_refuses_bad_sizes():
@@ -161,3 +173,123 @@ def test_library_exports_the_ssim_entry_points_and_refuses_bad_sizes():
     a.mode = L.GDR_SSIM_MS
     assert lib.gdr_ssim_forward(C.byref(a), None, st, None, st, None, None, None) == -1
     assert lib.gdr_ssim_backward(C.byref(a), None, st, None, st, None, None, None, st, None, None, None, None) == -1
+
+
+# ---- the inputs of ssim_cases.py discriminate: mutants of the restatement ---------------------------------------------
+# Each mutant is the restatement with one index wrong, in the way a kernel could be wrong.  On its NEW input (the one
+# test_gpu_ssim.py now runs) it must miss the true restatement by more than the bars the GPU test applies
+# (ssim_cases.beyond_bar); on the OLD inputs (what test_gpu_ssim.py fed before: one layout for X and Y, a uniform upstream
+# gradient, the Gaussian window, the five default weights) `old_sees` records whether it was visible at all.
+def _planes_grads(X, Y, r, op="ms_ssim", fwd_win=None, pool=None, weights=None, **kw):
+    """(per-sample value, [dX, dY]) of the restatement for the upstream gradient r over the (B, C) planes.  `fwd_win`
+    replaces the window in the value only (the gradient keeps the true one): a forward-only tap flip."""
+    X = X.detach().requires_grad_(True)
+    Y = Y.detach().requires_grad_(True)
+
+    def run(win):
+        if op == "ssim":
+            return R.ssim_planes(X, Y, data_range=1.0, win=win, **kw)
+        return R.ms_ssim_planes(X, Y, data_range=1.0, win=win, weights=weights, pool=pool, **kw)
+
+    true_win = kw.pop("win", None)
+    v = run(true_win)
+    grads = list(torch.autograd.grad(v, [X, Y], r))
+    if fwd_win is not None:
+        with torch.no_grad():
+            v = run(fwd_win)
+    return v.detach(), grads
+
+
+def _swapped_pool(x):
+    """pool2 with pady and padx exchanged (the output keeps its size): rows padded by w % 2, columns by h % 2."""
+    h, w = x.shape[-2:]
+    h2, w2 = (h + h % 2) // 2, (w + w % 2) // 2
+    x = F.pad(x, (h % 2, 2, w % 2, 2))[..., :2 * h2, :2 * w2]
+    B, Ch = x.shape[:2]
+    return x.reshape(B, Ch, h2, 2, w2, 2).sum(dim=(3, 5)) / 4
+
+
+def _through_x_layout(X, Y):
+    """Y's memory read through X's strides."""
+    flat = Y.contiguous().view(-1) if Y.is_contiguous() else Y.permute(0, 2, 3, 1).contiguous().view(-1)
+    assert flat.numel() == Y.numel()
+    return torch.as_strided(flat, X.shape, X.stride())
+
+
+def _five(w):
+    """Weights cut or padded to five levels (a level count or a coef stride written as the constant 5)."""
+    return tuple((list(w) + list(R.MS_WEIGHTS[len(w):]))[:5])
+
+
+def _mutant_pair(name, old):
+    """((value, grads) of the true restatement, (value, grads) of the mutant) on the new or the old input."""
+    B, Ch = 3, 2
+    if name.startswith("upstream"):
+        X, Y = SC.images((B, Ch, 60, 75), seed=11, dtype=torch.float64)
+        r = torch.full((B, Ch), 1.0 / Ch, dtype=torch.float64) if old else SC.upstream((B, Ch), 12, dtype=torch.float64)
+        rm = {"upstream_rolled_b": r.roll(1, 0), "upstream_rolled_c": r.roll(1, 1),
+              "upstream_transposed": r.t().reshape(B, Ch)}[name]
+        kw = dict(op="ms_ssim", win_size=3, weights=(0.3, 0.5, 0.4))
+        return _planes_grads(X, Y, r, **kw), _planes_grads(X, Y, rm, **kw)
+    r = torch.ones(B, Ch, dtype=torch.float64)
+    if name == "window_reversed_forward":
+        X, Y = SC.images((B, Ch, 60, 75), seed=20, dtype=torch.float64)
+        win = R.gauss_window(7, 1.0).double() if old else SC.asym_window(7, Ch).double().reshape(Ch, 7)[0]
+        return (_planes_grads(X, Y, r, op="ssim", win=win), _planes_grads(X, Y, r, op="ssim", win=win, fwd_win=win.flip(0)))
+    if name == "y_through_x_layout":
+        X, Y = SC.images((B, Ch, 60, 75), seed=80, dtype=torch.float64)
+        X, Y = SC.apply_layout(X, Y, "same" if old else "x_nhwc")
+        return _planes_grads(X, Y, r, op="ssim"), _planes_grads(X, _through_x_layout(X, Y), r, op="ssim")
+    if name == "pool_padding_swapped":
+        # old: (2, 3, 333, 251) of test_ms_ssim_odd_sizes..., whose level 1 is 167 x 126 (odd, even) -- cut to one plane here
+        shape = (1, 1, 333, 251) if old else (1, 1) + SC.AXIS_CASES["even_h_odd_w"]
+        X, Y = SC.images(shape, seed=2 if old else 70, dtype=torch.float64)
+        r = torch.ones(1, 1, dtype=torch.float64)
+        return _planes_grads(X, Y, r), _planes_grads(X, Y, r, pool=_swapped_pool)
+    if name == "weights_forced_to_five":
+        w, k, _ = SC.LEVEL_CASES["L3"]
+        w = R.MS_WEIGHTS if old else w
+        X, Y = SC.images((B, Ch, 60, 75), seed=63, dtype=torch.float64)
+        return _planes_grads(X, Y, r, win_size=3, weights=w), _planes_grads(X, Y, r, win_size=3, weights=_five(w))
+    raise ValueError(name)
+
+
+# mutant -> (the test of test_gpu_ssim.py whose input exposes it, did the old inputs see it?)
+SSIM_MUTANTS = {
+    "upstream_rolled_b": ("test_upstream_gradient_differs_for_every_plane", False),
+    "upstream_rolled_c": ("test_upstream_gradient_differs_for_every_plane", False),
+    "upstream_transposed": ("test_upstream_gradient_differs_for_every_plane", False),
+    "window_reversed_forward": ("test_asymmetric_window_is_a_correlation_forward_and_transposed_backward", False),
+    "y_through_x_layout": ("test_layouts_that_differ_between_x_and_y", False),
+    # the old odd sizes already had one level with an odd H beside an even W: the claim of the issue is dropped; the new
+    # sizes differ in parity at every level and in both directions
+    "pool_padding_swapped": ("test_axes_that_differ_at_every_level", True),
+    "weights_forced_to_five": ("test_level_counts_and_unequal_weights", False),
+}
+
+
+@pytest.mark.parametrize("name", list(SSIM_MUTANTS))
+def test_new_inputs_expose_the_mutant_and_the_old_ones_did_not(name):
+    import test_gpu_ssim
+
+    gpu_test, old_sees = SSIM_MUTANTS[name]
+    assert hasattr(test_gpu_ssim, gpu_test)
+    (v, g), (vm, gm) = _mutant_pair(name, old=False)
+    assert SC.beyond_bar(vm, gm, v, g), name
+    (v, g), (vm, gm) = _mutant_pair(name, old=True)
+    if old_sees:
+        assert SC.beyond_bar(vm, gm, v, g), name
+    else:      # not merely within the bars: identical
+        assert torch.equal(vm, v) and all(torch.equal(a, b) for a, b in zip(gm, g)), name
+
+
+def test_restatement_window_argument_is_a_correlation():
+    """`win=` in the restatement: the taps as given, along H then W, as F.conv2d applies a (C, 1, 1, k) tensor."""
+    X, _ = SC.images((1, 3, 40, 37), seed=4, dtype=torch.float64)
+    win = SC.asym_window(7, 3).double()
+    ref = F.conv2d(F.conv2d(X, win.transpose(2, 3), groups=3), win, groups=3)
+    assert torch.allclose(R.blur(X, R._window(11, 1.5, win)), ref, atol=1e-14)
+    assert not torch.allclose(R.blur(X, R._window(11, 1.5, win).flip(0)), ref, atol=1e-6)
+    Y = X.flip(-1).contiguous()
+    assert torch.equal(R.ssim(X, Y, data_range=1.0, win=win), R.ssim(X, Y, data_range=1.0, win=win.reshape(3, 7)[0]))
+    assert torch.equal(R.ssim(X, Y, data_range=1.0), R.ssim(X, Y, data_range=1.0, win=R.gauss_window(11, 1.5)))

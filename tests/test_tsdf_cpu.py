@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import tsdf_cases as TC
 import tsdf_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -205,3 +206,126 @@ def test_mesh_path_unposed_and_unknown():
         mesh_path_cameras(16, {"dataset_name": "unposed", "img_size": (32, 32)})
     with pytest.raises(ValueError):
         mesh_path_cameras(16, {"dataset_name": "nerf", "img_size": (32, 32)})
+
+
+def test_float_colour_staging_rule():
+    """make_view: p = rgb * 255 in fp32, truncated, clipped to 0..255, NaN -> 0; floor(rgb * 255) on [0, 1]."""
+    rgb = np.array([0.0, -0.0, 1.0, 254.9 / 255, 0.5, 256 / 255, 1.2, 1e30, np.inf, -0.3, -1e30, -np.inf, np.nan, 1 / 255],
+                   np.float32)
+    want = [0, 0, 255, 254, 127, 255, 255, 255, 255, 0, 0, 0, 0, int(np.float32(1 / 255) * np.float32(255))]
+    v = R.make_view(np.ones((1, 14), np.float32), np.repeat(rgb[None, :, None], 3, 2), 1, 1, 0, 0, np.eye(4), 4.0)
+    np.testing.assert_array_equal(v["rgb"][0, :, 0], want)
+    k = np.arange(256, dtype=np.float32) / np.float32(255)
+    v = R.make_view(np.ones((1, 256), np.float32), np.repeat(k[None, :, None], 3, 2), 1, 1, 0, 0, np.eye(4), 4.0)
+    np.testing.assert_array_equal(v["rgb"][0, :, 1], np.floor(k * np.float32(255)).astype(np.uint8))
+    u8 = np.arange(256, dtype=np.uint8).reshape(1, 256, 1).repeat(3, 2)
+    np.testing.assert_array_equal(R.make_view(np.ones((1, 256), np.float32), u8, 1, 1, 0, 0, np.eye(4), 4.0)["rgb"], u8)
+
+
+def test_cluster_cases_have_the_structure_they_are_there_for():
+    for name in ("strip_200k", "pairs", "one", "wave_plus_one"):
+        f, nv = TC.cluster_case(name)
+        assert f.dtype == np.int32 and f.max() < nv
+        lab, counts = R.clusters(f, nv)
+        assert len(lab) == len(f)
+        if name == "strip_200k":
+            assert len(counts) == 1 and len(f) == 200_000 and not (np.diff(f[:, 0]) == 1).all()
+        if name == "pairs":
+            assert len(counts) == 50_000 and (counts == 2).all()
+        if name == "one":
+            assert counts.tolist() == [1]
+        if name == "wave_plus_one":
+            assert len(f) == 65
+
+
+# ---- the inputs of tsdf_cases.py discriminate: mutants of the restatement ---------------------------------------------
+# Each mutant is tsdf_ref.fuse with one index wrong, in the way a kernel could be wrong.  On its NEW input (the one
+# test_gpu_mesh.py now runs) its blocks, masks or voxels must differ from the true restatement's at all (the GPU test asks
+# bit equality); on the OLD input (the builder test_gpu_mesh.py used before: square images, fx == fy, a centred principal
+# point, H % 4 == 0) `old_sees` records whether the mutant was visible.
+def _swap(views, a, b):
+    return [dict(v, **{a: v[b], b: v[a]}) for v in views]
+
+
+def _h_for_w(views):
+    """depth and colour read at v * H + u instead of v * W + u."""
+    out = []
+    for v in views:
+        H, W = v["depth"].shape
+        idx = (np.arange(H)[:, None] * H + np.arange(W)[None]) % (H * W)
+        out.append(dict(v, depth=v["depth"].reshape(-1)[idx], rgb=v["rgb"].reshape(-1, 3)[idx]))
+    return out
+
+
+def _fuse_mutant(name, views, voxel, stride):
+    trunc = 2 * voxel
+    if name == "fx_fy_swapped":
+        return R.fuse(_swap(views, "fx", "fy"), voxel, trunc, stride=stride)
+    if name == "cx_cy_swapped":
+        return R.fuse(_swap(views, "cx", "cy"), voxel, trunc, stride=stride)
+    if name == "h_for_w":
+        return R.fuse(_h_for_w(views), voxel, trunc, stride=stride)
+    if name == "partial_sample_dropped":     # sh = H / S, sw = W / S rounded down
+        cut = []
+        for v in views:
+            H, W = v["depth"].shape
+            d = v["depth"].copy()
+            d[(H // stride) * stride:] = 0
+            d[:, (W // stride) * stride:] = 0
+            cut.append(dict(v, depth=d))
+        blocks, mask = R.allocate(cut, voxel, trunc, stride=stride)
+        return (blocks, mask) + R.integrate(views, blocks, mask, voxel, trunc)
+    blocks, mask = R.allocate(views, voxel, trunc, stride=stride)
+    if name == "mask_bit_in_word_0":         # view k recorded as bit k % 32 of word 0
+        folded = np.zeros_like(mask)
+        for k in range(mask.shape[1]):
+            folded[:, k % 32] |= mask[:, k]
+        return (blocks, folded) + R.integrate(views, blocks, folded, voxel, trunc)
+    if name == "block_origin_off_by_one":    # the voxels of block b computed from b + (1, 0, 0)
+        return (blocks, mask) + R.integrate(views, blocks + np.array([1, 0, 0]), mask, voxel, trunc)
+    raise ValueError(name)
+
+
+def _old_input(n_views=6):
+    return TC.ref_views(TC.old_views(n_views // 3, 64, noise=0.003, holes=True)), 0.02, 4
+
+
+def _new_input(kind):
+    if kind == "asym":          # test_gpu_asymmetric_camera_model, test_gpu_sampling_strides[4]
+        return TC.ref_views(TC.sphere_views(6, seed=1)), 0.012, 4
+    if kind == "views_33":      # test_gpu_view_mask_words[33]
+        return TC.ref_views(TC.sphere_views(33, cam=TC.SMALL, seed=33)), 0.02, 4
+    if kind == "negative":      # test_gpu_off_origin_objects[negative_octant] (fewer views, coarser voxels)
+        return TC.ref_views(TC.sphere_views(4, spheres=TC.OFF_ORIGIN["negative_octant"], seed=7)), 0.012, 4
+    raise ValueError(kind)
+
+
+# mutant -> (the new input that exposes it, the test of test_gpu_mesh.py that runs it, did the old inputs see it?)
+TSDF_MUTANTS = {
+    "fx_fy_swapped": ("asym", "test_gpu_asymmetric_camera_model", False),
+    "cx_cy_swapped": ("asym", "test_gpu_asymmetric_camera_model", False),
+    "h_for_w": ("asym", "test_gpu_asymmetric_camera_model", False),
+    "partial_sample_dropped": ("asym", "test_gpu_sampling_strides", False),
+    # test_gpu_matches_restatement already had 42 views, so a view >= 32 folded into word 0 was visible: the claim is
+    # dropped; what is new is 3 and 4 words and V an exact multiple of 32
+    "mask_bit_in_word_0": ("views_33", "test_gpu_view_mask_words", True),
+    # an origin off by one block moves every voxel, wherever the object is: the old inputs saw it; the new ones add
+    # coordinates that are all negative or far from 0
+    "block_origin_off_by_one": ("negative", "test_gpu_off_origin_objects", True),
+}
+
+
+def _differs(a, b):
+    return any(x.shape != y.shape or not np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("name", list(TSDF_MUTANTS))
+def test_new_inputs_expose_the_mutant_and_the_old_ones_did_not(name):
+    import test_gpu_mesh
+
+    kind, gpu_test, old_sees = TSDF_MUTANTS[name]
+    assert hasattr(test_gpu_mesh, gpu_test)
+    views, voxel, stride = _new_input(kind)
+    assert _differs(_fuse_mutant(name, views, voxel, stride), R.fuse(views, voxel, 2 * voxel, stride=stride)), name
+    views, voxel, stride = _old_input(42 if name == "mask_bit_in_word_0" else 6)
+    assert _differs(_fuse_mutant(name, views, voxel, stride), R.fuse(views, voxel, 2 * voxel, stride=stride)) == old_sees, name

@@ -3,7 +3,8 @@
 The semantics are those of Open3D's ScalableTSDFVolume (RGB8 colour) as published; parity with Open3D itself is unpinned.
 All arithmetic is fp32 in the order written below, so the HIP kernels (built with -ffp-contract=off) reproduce it bit for bit.
 
-Depth      D(v, u) is set to 0 where it is not finite, <= 0 or > depth_trunc.  Colour is uint8 (floor(rgb * 255) for float input).
+Depth      D(v, u) is set to 0 where it is not finite, <= 0 or > depth_trunc.  Colour is uint8; float input is staged as
+           p = rgb * 255 in fp32, truncated toward zero, then clipped to 0..255, and NaN gives 0 (floor(rgb * 255) on [0, 1]).
 Allocation pixels with u % S == 0, v % S == 0 (S = depth_sampling_stride) and d > 0: q = ((u - cx) d / fx, (v - cy) d / fy, d),
            p = c2w q (c2w = inverse of E in f64, cast to f32); every block b with floor((p - trunc) / L) <= b <= floor((p + trunc) / L)
            per axis (L = R * voxel) is marked as touched by the view.  Blocks are ordered by (bz, by, bx).
@@ -92,7 +93,12 @@ def make_view(depth, rgb, fx, fy, cx, cy, extrinsic, depth_trunc):
     with np.errstate(invalid="ignore"):
         d = np.where(np.isfinite(d) & (d > 0) & (d <= f32(depth_trunc)), d, f32(0)).astype(f32)
     rgb = np.asarray(rgb)
-    c = rgb if rgb.dtype == np.uint8 else np.asarray(rgb * 255, dtype=np.uint8)
+    if rgb.dtype == np.uint8:
+        c = rgb
+    else:   # truncate, then clip to 0..255; NaN gives 0 (astype(uint8) alone is undefined out of range)
+        with np.errstate(invalid="ignore", over="ignore"):
+            p = rgb.astype(f32) * f32(255)
+            c = np.where(np.isnan(p), f32(0), np.clip(np.trunc(p), f32(0), f32(255))).astype(np.uint8)
     E = np.asarray(extrinsic, dtype=np.float64)
     return dict(depth=d, rgb=c.reshape(d.shape[0], d.shape[1], 3), fx=f32(fx), fy=f32(fy), cx=f32(cx), cy=f32(cy),
                 E=E.astype(f32), c2w=np.linalg.inv(E).astype(f32))
