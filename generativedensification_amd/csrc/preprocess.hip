@@ -116,6 +116,28 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_kernel(
         const float pvx = cam.v[0] * px_ + cam.v[4] * py_ + cam.v[8] * pz_ + cam.v[12];
         const float pvy = cam.v[1] * px_ + cam.v[5] * py_ + cam.v[9] * pz_ + cam.v[13];
         const float pvz = cam.v[2] * px_ + cam.v[6] * py_ + cam.v[10] * pz_ + cam.v[14];
+        // cov3D of EVERY Gaussian, also of those this view culls: a render group's multi-view K8+K9 reads ONE view's copy
+        // for all its views, and a Gaussian behind this camera's near plane may be visible to the next one
+        if (cov3D_precomp) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * i + k];
+        } else {
+            float4 q = reinterpret_cast<const float4*>(rotations)[i];
+            float sc0 = scales[3 * i], sc1 = scales[3 * i + 1], sc2 = scales[3 * i + 2];
+            if (flags & GDR_IN_RAW_ROTATIONS) { float inv_n; q = act_normalize(q, &inv_n); }
+            if (flags & GDR_IN_RAW_SCALES) { sc0 = expf(sc0); sc1 = expf(sc1); sc2 = expf(sc2); }
+            float R[9], Mm[9];
+            quat_to_R(q.x, q.y, q.z, q.w, R);
+            const float s[3] = {scale_modifier * sc0, scale_modifier * sc1, scale_modifier * sc2};
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) Mm[r * 3 + k] = R[r * 3 + k] * s[k];
+#define SIG(a_, b_) ((Mm[a_ * 3 + 0] * Mm[b_ * 3 + 0] + Mm[a_ * 3 + 1] * Mm[b_ * 3 + 1]) + Mm[a_ * 3 + 2] * Mm[b_ * 3 + 2])
+            c6[0] = SIG(0, 0); c6[1] = SIG(0, 1); c6[2] = SIG(0, 2);
+            c6[3] = SIG(1, 1); c6[4] = SIG(1, 2); c6[5] = SIG(2, 2);
+#undef SIG
+        }
         bool ok = pvz > 0.2f;  // near cull (A.1-1); no x/y frustum test when prefiltered=False
         if (ok) {
             const float phx = cam.p[0] * px_ + cam.p[4] * py_ + cam.p[8] * pz_ + cam.p[12];
@@ -124,26 +146,6 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_kernel(
             const float p_w = 1.0f / (phw + 0.0000001f);
             const float ppx = phx * p_w, ppy = phy * p_w;
 
-            if (cov3D_precomp) {
-#pragma unroll
-                for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * i + k];
-            } else {
-                float4 q = reinterpret_cast<const float4*>(rotations)[i];
-                float sc0 = scales[3 * i], sc1 = scales[3 * i + 1], sc2 = scales[3 * i + 2];
-                if (flags & GDR_IN_RAW_ROTATIONS) { float inv_n; q = act_normalize(q, &inv_n); }
-                if (flags & GDR_IN_RAW_SCALES) { sc0 = expf(sc0); sc1 = expf(sc1); sc2 = expf(sc2); }
-                float R[9], Mm[9];
-                quat_to_R(q.x, q.y, q.z, q.w, R);
-                const float s[3] = {scale_modifier * sc0, scale_modifier * sc1, scale_modifier * sc2};
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) Mm[r * 3 + k] = R[r * 3 + k] * s[k];
-#define SIG(a_, b_) ((Mm[a_ * 3 + 0] * Mm[b_ * 3 + 0] + Mm[a_ * 3 + 1] * Mm[b_ * 3 + 1]) + Mm[a_ * 3 + 2] * Mm[b_ * 3 + 2])
-                c6[0] = SIG(0, 0); c6[1] = SIG(0, 1); c6[2] = SIG(0, 2);
-                c6[3] = SIG(1, 1); c6[4] = SIG(1, 2); c6[5] = SIG(2, 2);
-#undef SIG
-            }
             Ewa e;
             ewa(cam, pvx, pvy, pvz, c6, focal_x, focal_y, tanx, tany, e);
             const float det = e.a * e.c - e.b * e.b;

@@ -67,7 +67,9 @@ void oracle_preprocess_fwd(int N, int deg, int M, const real* means3D, const rea
         for (int k = 0; k < 4; ++k) conic_opacity[4 * i + k] = 0;
         for (int k = 0; k < 4; ++k) rect[4 * i + k] = 0;
         for (int k = 0; k < 3; ++k) { rgb[3 * i + k] = 0; clamped[3 * i + k] = 0; }
-        if (!cov3D_precomp) for (int k = 0; k < 6; ++k) cov3D[6 * i + k] = 0;
+        /* cov3D is view-independent and stored for EVERY Gaussian, culled or not (the product shares one view's copy
+         * between the views of a render group) */
+        if (!cov3D_precomp) compute_cov3D(scales + 3 * i, scale_modifier, rotations + 4 * i, cov3D + 6 * i);
 
         const real* p = means3D + 3 * i;
         real pv[3];
@@ -83,7 +85,6 @@ void oracle_preprocess_fwd(int N, int deg, int M, const real* means3D, const rea
         if (cov3D_precomp) {
             c6 = cov3D_precomp + 6 * i;
         } else {
-            compute_cov3D(scales + 3 * i, scale_modifier, rotations + 4 * i, cov3D + 6 * i);
             c6 = cov3D + 6 * i;
         }
 

@@ -75,13 +75,17 @@ def gen_minicam():
         cam = ref_utils.MiniCam(c2w, w, h, torch.tensor(fovy), torch.tensor(fovx), 1.1, 2.7, "cpu")
         save(f"minicam_lookat{k}.npz", c2w=c2w, width=w, height=h, fovy=fovy, fovx=fovx, znear=1.1, zfar=2.7,
              **cam_arrays(cam))
+    # fovx and fovy far apart, W != H, eye inside the scene cube looking past its centre (tests/camera_cases.py)
+    c2w = look_at_c2w(torch.tensor([0.35, 0.2, 0.1]), torch.tensor([-0.3, -0.1, 0.05]))
+    cam = ref_utils.MiniCam(c2w, 206, 110, torch.tensor(0.45), torch.tensor(1.1), 0.1, 5.0, "cpu")
+    save("minicam_fovxy.npz", c2w=c2w, width=206, height=110, fovy=0.45, fovx=1.1, znear=0.1, zfar=5.0, **cam_arrays(cam))
 
 
 # ---- 2. Renderer.render_img (lightning/renderer.py:209-272) through the reference class ----
-def gen_render_img(name, n, h, w, deg, sigma0, seed, bg, cam_eye):
+def gen_render_img(name, n, h, w, deg, sigma0, seed, bg, cam_eye, cam_target=None, fovx=0.75, fovy=0.75, znear=1.1, zfar=2.7):
     scene = make_scene(n, seed, sh_degree=deg, sigma0=sigma0)
-    c2w = look_at_c2w(torch.tensor(cam_eye))
-    cam = ref_utils.MiniCam(c2w, w, h, torch.tensor(0.75), torch.tensor(0.75), 1.1, 2.7, "cpu")
+    c2w = look_at_c2w(torch.tensor(cam_eye), None if cam_target is None else torch.tensor(cam_target))
+    cam = ref_utils.MiniCam(c2w, w, h, torch.tensor(fovy), torch.tensor(fovx), znear, zfar, "cpu")
     r = ref_renderer.Renderer(sh_degree=deg, white_background=True)
     r.set_bg_color(torch.tensor(bg, dtype=torch.float32))
     leaves = {k: v.clone().requires_grad_(True) for k, v in scene.items()}
@@ -95,7 +99,8 @@ def gen_render_img(name, n, h, w, deg, sigma0, seed, bg, cam_eye):
     loss = view_loss(out, target)
     grads = torch.autograd.grad(loss, list(leaves.values()) + [ssp])
     o = rec[0]
-    save(name, n=n, h=h, w=w, sh_degree=deg, bg=np.asarray(bg, np.float32), c2w=c2w, fov=0.75, znear=1.1, zfar=2.7,
+    save(name, n=n, h=h, w=w, sh_degree=deg, bg=np.asarray(bg, np.float32), c2w=c2w,
+         **(dict(fov=fovx) if fovx == fovy else dict(fovx=fovx, fovy=fovy)), znear=znear, zfar=zfar,
          **{f"in_{k}": v for k, v in scene.items()}, **cam_arrays(cam), target=target,
          image=out["image"], depth=out["depth"], acc_map=out["acc_map"], loss=loss,
          **{f"grad_{k}": g for k, g in zip(list(leaves) + ["screenspace_points"], grads)},
@@ -137,4 +142,7 @@ if __name__ == "__main__":
     gen_minicam()
     gen_render_img("render_img_deg3.npz", 1500, 80, 112, 3, (0.03, 0.008), 101, (1.0, 1.0, 1.0), [1.5, 0.9, 0.7])
     gen_render_img("render_img_deg1.npz", 2500, 64, 64, 1, (0.0052, 0.02), 102, (0.5, 0.5, 0.5), [-1.2, 1.3, -0.6])
+    # fovx != fovy, W != H, eye on an edge of the scene cube: Gaussians in the frustum clamp and near the near plane
+    gen_render_img("render_img_fovxy.npz", 2500, 78, 52, 1, (0.02, 0.006), 104, (0.2, 0.7, 0.4), [0.5, -0.5, 0.1],
+                   cam_target=[0.0, 0.1, 0.0], fovx=0.4, fovy=0.8, znear=0.1, zfar=5.0)
     gen_legacy("legacy_render_colors.npz", 1200, 48, 72, 103)

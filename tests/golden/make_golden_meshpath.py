@@ -7,7 +7,7 @@ reference's own camera code, which is not part of this repository.  Stand-ins ar
 injected for what the camera path does not use: `sklearn.cluster` (imported by dataLoader/utils.py), `jaxtyping` and
 `tools.camera_utils` (the 'unposed' pose interpolation), and the `dataLoader` package (its utils.py is loaded by file).
 Per camera it records world_view_transform, full_proj_transform, camera_center, FoVx / FoVy and get_rays() at 16 x 16, for
-both families with and without `sample` / `fov`.  Usage: python tests/golden/make_golden_meshpath.py
+both families with and without `sample` / `fov`, and once at 22 x 14 with fovx = 1.1, fovy = 0.45.  Usage: python tests/golden/make_golden_meshpath.py
 """
 import importlib.util
 import os
@@ -58,10 +58,10 @@ def transform(seed):
     return T
 
 
-def record(name, dataset_name, sample, fov):
-    data = types.SimpleNamespace(dataset_name=dataset_name, img_size=list(SIZE))
+def record(name, dataset_name, sample, fov, size=SIZE, prefix="mesh_path_"):
+    data = types.SimpleNamespace(dataset_name=dataset_name, img_size=list(size))
     cams = uni_mesh_path(16, data, sample, fov)
-    out = dict(dataset_name=dataset_name, img_size=np.array(SIZE), n=16)
+    out = dict(dataset_name=dataset_name, img_size=np.array(size), n=16)
     if sample is not None:
         out["transform_mats"] = sample["transform_mats"].numpy()
     if fov is not None:
@@ -71,7 +71,7 @@ def record(name, dataset_name, sample, fov):
                     ("fov_xy", lambda c: torch.tensor([float(c.FoVx), float(c.FoVy)])),
                     ("rays", lambda c: c.get_rays()[0])):
         out[key] = np.stack([fn(c).detach().cpu().numpy() for c in cams]).astype(np.float32)
-    path = os.path.join(HERE, f"mesh_path_{name}.npz")
+    path = os.path.join(HERE, f"{prefix}{name}.npz")
     np.savez_compressed(path, **out)
     print(f"wrote {os.path.basename(path)}: {len(cams)} cameras, {os.path.getsize(path) / 1024:.1f} KiB")
 
@@ -83,3 +83,6 @@ if __name__ == "__main__":
     record("instant3d", "instant3d", None, None)
     record("mvgen_sample_fov", "mvgen", {"transform_mats": transform(2)[None, None]}, fov)
     record("co3d_fov", "co3d", None, fov)
+    # fovx and fovy far apart on a non-square image (width 22, height 14): an x / y mix-up shows in the projection and the rays
+    # (cameras only: its own prefix keeps it out of the mesh-fusion tests that take every mesh_path_*.npz)
+    record("instant3d_fovxy", "instant3d", None, torch.tensor([1.1, 0.45]), size=(22, 14), prefix="pathcam_")

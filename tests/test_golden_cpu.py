@@ -36,6 +36,11 @@ def test_minicam_known_answer_from_survey():
     np.testing.assert_array_equal(g["camera_center"], [0, 0, 2])  # sign quirk of lightning/utils.py:48
 
 
+def _fovs(g):
+    """(fovx, fovy) of a render_img fixture: `fov` where they are equal, `fovx`, `fovy` where they differ."""
+    return (float(g["fovx"]), float(g["fovy"])) if "fovx" in g else (float(g["fov"]),) * 2
+
+
 def _mirror_with_oracle(monkeypatch):
     """The repo's Renderer mirror with the oracle stand-in in place of the HIP rasterizer:
     isolates the HOST logic (activations, carrier, clamp, permutes) for a CPU check."""
@@ -48,15 +53,15 @@ def _mirror_with_oracle(monkeypatch):
     return R, st
 
 
-@pytest.mark.parametrize("name", ["render_img_deg3.npz", "render_img_deg1.npz"])
+@pytest.mark.parametrize("name", ["render_img_deg3.npz", "render_img_deg1.npz", "render_img_fovxy.npz"])
 def test_renderer_mirror_reproduces_reference_render_img(oracle_built, monkeypatch, name):
     from generativedensification_amd.camera import MiniCam
     from generativedensification_amd.synthetic import view_loss
 
     g = _load(name)
     R, st = _mirror_with_oracle(monkeypatch)
-    cam = MiniCam(torch.from_numpy(g["c2w"]), int(g["w"]), int(g["h"]), torch.tensor(float(g["fov"])),
-                  torch.tensor(float(g["fov"])), float(g["znear"]), float(g["zfar"]), "cpu")
+    cam = MiniCam(torch.from_numpy(g["c2w"]), int(g["w"]), int(g["h"]), torch.tensor(_fovs(g)[1]),
+                  torch.tensor(_fovs(g)[0]), float(g["znear"]), float(g["zfar"]), "cpu")
     r = R.Renderer(sh_degree=int(g["sh_degree"]), white_background=True)
     r.set_bg_color(torch.from_numpy(g["bg"]))
     leaves = {k: torch.from_numpy(g[f"in_{k}"]).clone().requires_grad_(True)

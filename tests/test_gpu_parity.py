@@ -106,8 +106,13 @@ import os
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+def _fovs(g):
+    """(fovx, fovy) of a render_img fixture: `fov` where they are equal, `fovx`, `fovy` where they differ."""
+    return (float(g["fovx"]), float(g["fovy"])) if "fovx" in g else (float(g["fov"]),) * 2
+
+
 @pytest.mark.parametrize("fused", [False, True])
-@pytest.mark.parametrize("name", ["render_img_deg3.npz", "render_img_deg1.npz"])
+@pytest.mark.parametrize("name", ["render_img_deg3.npz", "render_img_deg1.npz", "render_img_fovxy.npz"])
 def test_product_renderer_on_gpu_matches_golden_render_img(name, fused):
     """The repo's Renderer mirror + HIP rasterizer (the full product path, through the C ABI)
     against what the reference's own Renderer.render_img produced on the fixture."""
@@ -117,8 +122,8 @@ def test_product_renderer_on_gpu_matches_golden_render_img(name, fused):
 
     g = dict(np.load(os.path.join(GOLD, name)))
     dev = torch.device("cuda:0")
-    cam = MiniCam(torch.from_numpy(g["c2w"]), int(g["w"]), int(g["h"]), torch.tensor(float(g["fov"])),
-                  torch.tensor(float(g["fov"])), float(g["znear"]), float(g["zfar"]), dev)
+    cam = MiniCam(torch.from_numpy(g["c2w"]), int(g["w"]), int(g["h"]), torch.tensor(_fovs(g)[1]),
+                  torch.tensor(_fovs(g)[0]), float(g["znear"]), float(g["zfar"]), dev)
     r = Renderer(sh_degree=int(g["sh_degree"]), white_background=True, fused=fused)
     r.set_bg_color(torch.from_numpy(g["bg"]))
     leaves = {k: torch.from_numpy(g[f"in_{k}"]).to(dev).requires_grad_(True)

@@ -174,13 +174,16 @@ def test_product_refuses_cpu_tensors():
 
 
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "mesh_path_*.npz")))
+# cameras only, fovx = 1.1 and fovy = 0.45 on a 22 x 14 image: PathCamera(c2w, w, h, fovy, fovx, ...) with the two far apart
+PATHCAM_FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "pathcam_*.npz")))
 
 
 def test_fixtures_present():
-    assert len(FIXTURES) == 5
+    assert len(FIXTURES) == 5 and len(PATHCAM_FIXTURES) == 1
 
 
-@pytest.mark.parametrize("path", FIXTURES, ids=[os.path.basename(p)[10:-4] for p in FIXTURES])
+@pytest.mark.parametrize("path", FIXTURES + PATHCAM_FIXTURES,
+                         ids=[os.path.basename(p)[10:-4] for p in FIXTURES] + [os.path.basename(p)[:-4] for p in PATHCAM_FIXTURES])
 def test_mesh_path_cameras_match_the_reference(path):
     from generativedensification_amd.mesh import mesh_path_cameras   # (camera.py, re-exported with the mesh path)
 

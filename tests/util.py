@@ -158,6 +158,17 @@ def assert_image_parity(h, o, tag, mask=None):
     return nc, ft, px, p
 
 
+def assert_rendered_parity(color, depth, alpha, o, tag):
+    """The colour / depth / alpha part of assert_image_parity, for entries that hand out no n_contrib / final_T."""
+    bad = np.zeros(np.asarray(o["alpha"]).shape[1:], bool)
+    for k, x in (("color", color), ("depth", depth), ("alpha", alpha)):
+        x, y = np.asarray(x, np.float64), np.asarray(o[k], np.float64)
+        assert rel_inf(x, y) < 5e-3, (tag, k)
+        bad |= (np.abs(x - y) > 1e-5 + 1e-4 * np.abs(y)).any(axis=0)
+    p = psnr(np.clip(color, 0, 1), np.clip(o["color"], 0, 1))
+    assert int(bad.sum()) <= MAX_IMAGE_PIXELS and p > 60.0, (tag, dict(image_pixels=int(bad.sum()), psnr=p))
+
+
 def psnr(a, b):
     mse = float(((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2).mean())
     return 10 * math.log10(1.0 / max(mse, 1e-30))
