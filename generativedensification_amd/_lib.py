@@ -149,6 +149,17 @@ class GdrTsdfArgs(C.Structure):   # include/gdr.h gdr_tsdf_args
                 ("n_blocks", C.c_int32), ("voxel", C.c_float), ("trunc", C.c_float), ("lo", C.c_int32 * 3),
                 ("dims", C.c_int32 * 3)]
 
+GDR_ATTN_MAX_SEQLEN = 256
+GDR_ATTN_F16, GDR_ATTN_BF16 = 0, 1
+GDR_ATTN_HEAD_DIMS = (8, 16, 32, 64)
+
+
+class GdrAttnArgs(C.Structure):   # include/gdr.h gdr_attn_args
+    _fields_ = [("total", C.c_int32), ("batch", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("max_seqlen", C.c_int32),
+                ("fixed_len", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_float),
+                ("reserved2", C.c_float)]
+
+
 # every symbol include/gdr.h and include/gsr.h declare, with its prototype
 _PROTOS = {
     "gdr_abi_version": (C.c_int, []),
@@ -262,6 +273,11 @@ _PROTOS = {
     "gdr_tsdf_mc_count": (C.c_int, [C.POINTER(GdrTsdfArgs)] + [C.c_void_p] * 9),
     "gdr_tsdf_mc_emit": (C.c_int, [C.POINTER(GdrTsdfArgs)] + [C.c_void_p] * 11),
     "gdr_tsdf_clusters": (C.c_int, [C.c_int32] + [C.c_void_p] * 8),
+    "gdr_attn_lse_bytes": (C.c_size_t, [C.POINTER(GdrAttnArgs)]),
+    "gdr_attn_forward": (C.c_int, [C.POINTER(GdrAttnArgs), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "gdr_attn_backward": (C.c_int, [C.POINTER(GdrAttnArgs), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

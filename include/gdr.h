@@ -620,6 +620,35 @@ int gdr_tsdf_mc_emit(const gdr_tsdf_args* a, const int32_t* cell_block, const in
 int gdr_tsdf_clusters(int32_t F, const int64_t* keys, const int64_t* tri_of, int32_t* parent, uint32_t* root_rank,
                       int32_t* label, int32_t* counts, void* scratch, void* stream);
 
+/* ---- variable-length packed-QKV attention for short sequences (csrc/attn.hip; added in v17, backward-compatible) -------
+ * The one flash_attn entry point of the reference's point decoder (flash_attn_varlen_qkvpacked_func, dropout 0, no mask):
+ * per sequence b = rows [cu_seqlens[b], cu_seqlens[b + 1]) and head h, O = softmax(scale Q K^T) V over the key axis.
+ * qkv: (total, 3, H, D) fp16 or bf16 read through element strides (token, q/k/v, head, channel) — a slice of a wider buffer
+ * is read in place; cu_seqlens: batch + 1 device int32, or NULL: sequence b = rows [b * fixed_len, (b + 1) * fixed_len).
+ * out: (total, H, D) dense in the input dtype, 16-byte aligned; lse: (H, total) dense f32 (gdr_attn_lse_bytes), the
+ * per-row log-sum-exp of the scaled scores, written by forward and read by backward.  backward: dout (total, H, D) through
+ * its element strides, dqkv (total, 3, H, D) dense, 16-byte aligned.  Scores, softmax and every accumulation are f32.
+ * Rows at or beyond cu_seqlens[batch] (fixed_len * batch) are ZERO in out, lse and dqkv.  Envelope: D in {8, 16, 32, 64},
+ * H >= 1, 1 <= max_seqlen <= GDR_ATTN_MAX_SEQLEN, any 0 <= length <= max_seqlen mixed in one call; anything else is refused
+ * before any launch.  cu_seqlens is never read by the host: boundaries are clamped to [0, total] on the device and a
+ * sequence longer than max_seqlen is cut (its further rows are not written).  One launch each, no atomics: two runs are
+ * bitwise equal.  No host synchronisation. */
+#define GDR_ATTN_MAX_SEQLEN 256
+#define GDR_ATTN_F16 0
+#define GDR_ATTN_BF16 1
+typedef struct gdr_attn_args {
+    int32_t total, batch, H, D;
+    int32_t max_seqlen, fixed_len;   /* fixed_len: used only when cu_seqlens == NULL */
+    int32_t dtype, reserved;         /* GDR_ATTN_F16 / GDR_ATTN_BF16 */
+    float scale, reserved2;          /* softmax scale (the caller resolves the default D^-0.5) */
+} gdr_attn_args;
+size_t gdr_attn_lse_bytes(const gdr_attn_args* a);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_attn_forward(const gdr_attn_args* a, const void* qkv, const int64_t* qkv_strides, const int32_t* cu_seqlens,
+                     void* out, float* lse, void* stream);
+int gdr_attn_backward(const gdr_attn_args* a, const void* dout, const int64_t* dout_strides, const void* qkv,
+                      const int64_t* qkv_strides, const int32_t* cu_seqlens, const void* out, const float* lse, void* dqkv,
+                      void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
