@@ -306,6 +306,10 @@ _PROTOS = {
     "gsr_view_loss_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_float] * 5 + [C.c_void_p] * 5),
     "gsr_knn_cells": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "gsr_knn_mean_dist2": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_knn_grid": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gsr_knn_cells_axes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsr_knn_mean_dist2_counted": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "gsr_preprocess_forward_views": (C.c_int, [C.c_int32, C.POINTER(GdrSettings), C.POINTER(GsrInputs), C.POINTER(GdrGeom),
                                                C.POINTER(C.c_void_p), C.c_void_p]),
     "gsr_render_backward": (C.c_int, [C.POINTER(GdrSettings), C.c_int32, C.POINTER(GdrGeom), C.POINTER(GdrBinning),

@@ -1884,8 +1884,37 @@ int gsr_view_loss_backward(const float* color, const float* allmap, const float*
 
 int gsr_knn_cells(const float* points, int32_t N, const float* bbox, int32_t G, int32_t* cell, void* stream) {
     if (N < 0 || G < 1 || G > 1024 || (N > 0 && (!points || !bbox || !cell))) { set_error("gsr_knn_cells: bad argument", hipSuccess); return GDR_ERR_INVALID_ARG; }
-    hipError_t e = launch_knn_cells(points, N, bbox, G, cell, (hipStream_t)stream);
+    hipError_t e = launch_knn_cells(points, N, bbox, nullptr, G, cell, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail("knn_cells", e);
+    return GDR_OK;
+}
+
+int gsr_knn_grid(const float* bbox, int32_t target_cells, int32_t max_cells, int32_t forced_G, int32_t* gdim, void* stream) {
+    if (!bbox || !gdim || target_cells < 1 || max_cells < 1 || forced_G < 0 || forced_G > 1024 ||
+        (forced_G > 0 && (int64_t)forced_G * forced_G * forced_G > (int64_t)max_cells)) {
+        set_error("gsr_knn_grid: bad argument", hipSuccess);
+        return GDR_ERR_INVALID_ARG;
+    }
+    hipError_t e = launch_knn_grid(bbox, target_cells, max_cells, forced_G, gdim, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("knn_grid", e);
+    return GDR_OK;
+}
+
+int gsr_knn_cells_axes(const float* points, int32_t N, const float* bbox, const int32_t* gdim, int32_t* cell, void* stream) {
+    if (N < 0 || !gdim || (N > 0 && (!points || !bbox || !cell))) { set_error("gsr_knn_cells_axes: bad argument", hipSuccess); return GDR_ERR_INVALID_ARG; }
+    hipError_t e = launch_knn_cells(points, N, bbox, gdim, 0, cell, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("knn_cells", e);
+    return GDR_OK;
+}
+
+int gsr_knn_mean_dist2_counted(const float* points_sorted, int32_t N, const float* bbox, const int32_t* gdim,
+                               const int32_t* cell_start, float* out, uint32_t* work, void* stream) {
+    if (N < 0 || !gdim || (N > 0 && (!points_sorted || !bbox || !cell_start || !out))) {
+        set_error("gsr_knn_mean_dist2_counted: bad argument", hipSuccess);
+        return GDR_ERR_INVALID_ARG;
+    }
+    hipError_t e = launch_knn_mean_dist2(points_sorted, N, bbox, gdim, 0, cell_start, out, work, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail("knn_mean_dist2", e);
     return GDR_OK;
 }
 
@@ -1895,7 +1924,7 @@ int gsr_knn_mean_dist2(const float* points_sorted, int32_t N, const float* bbox,
         set_error("gsr_knn_mean_dist2: bad argument", hipSuccess);
         return GDR_ERR_INVALID_ARG;
     }
-    hipError_t e = launch_knn_mean_dist2(points_sorted, N, bbox, G, cell_start, out, (hipStream_t)stream);
+    hipError_t e = launch_knn_mean_dist2(points_sorted, N, bbox, nullptr, G, cell_start, out, nullptr, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail("knn_mean_dist2", e);
     return GDR_OK;
 }

@@ -202,9 +202,12 @@ hipError_t launch_surfel_loss_bwd(const float* color, const float* allmap, const
                                   float w_alpha, const float* g, float* scratch, float* dL_dcolor, float* dL_dallmap,
                                   hipStream_t st);
 
-hipError_t launch_knn_cells(const float* pts, int N, const float* bbox, int G, int32_t* cell, hipStream_t st);
-hipError_t launch_knn_mean_dist2(const float* pts_sorted, int N, const float* bbox, int G, const int32_t* cell_start,
-                                 float* out, hipStream_t st);
+// gdim: device cells per axis (nullptr = G on every axis); work: per-point candidate count or nullptr
+hipError_t launch_knn_grid(const float* bbox, int target, int cap, int forced, int32_t* gdim, hipStream_t st);
+hipError_t launch_knn_cells(const float* pts, int N, const float* bbox, const int32_t* gdim, int G, int32_t* cell,
+                            hipStream_t st);
+hipError_t launch_knn_mean_dist2(const float* pts_sorted, int N, const float* bbox, const int32_t* gdim, int G,
+                                 const int32_t* cell_start, float* out, uint32_t* work, hipStream_t st);
 
 size_t sort_hist_bytes(uint64_t D);
 hipError_t launch_words_differ(const void* a, const void* b, uint64_t n_bytes, uint32_t* flag, hipStream_t st);

@@ -170,10 +170,22 @@ int gsr_view_loss_backward(const float* color, const float* allmap, const float*
  *   gsr_knn_cells:      cell[i] = (cz*G + cy)*G + cx of point i in the G^3 grid over bbox (device float[6]: min, max)
  *   gsr_knn_mean_dist2: points_sorted = the points in ascending cell order, cell_start = (G^3 + 1) exclusive prefix;
  *                       out is in the SAME (sorted) order.  Exact (growing cubic shells until the third best is closer
- *                       than the searched cube's nearest face). */
+ *                       than the searched cube's nearest face).
+ * bbox need not contain the points: a point outside it is binned into the nearest edge cell and the search stays exact.
+ * The same two stages with cells chosen per axis, on the device (no host wait for the extents):
+ *   gsr_knn_grid:       gdim (device int32[3]) = cells per axis x,y,z for about target_cells near-cubic cells over bbox,
+ *                       Gx*Gy*Gz <= max_cells; an axis thinner than one such cell gets 1 cell (planes, lines, coincident
+ *                       clouds).  forced_G > 0: forced_G on every axis (forced_G^3 <= max_cells).
+ *   gsr_knn_cells_axes: cell[i] = (cz*Gy + cy)*Gx + cx
+ *   gsr_knn_mean_dist2_counted: cell_start = (Gx*Gy*Gz + 1) exclusive prefix; work (device uint32[N], sorted order, or
+ *                       NULL) = the number of candidate points whose distance was evaluated for each point. */
 int gsr_knn_cells(const float* points, int32_t N, const float* bbox, int32_t G, int32_t* cell, void* stream);
 int gsr_knn_mean_dist2(const float* points_sorted, int32_t N, const float* bbox, int32_t G, const int32_t* cell_start,
                        float* out, void* stream);
+int gsr_knn_grid(const float* bbox, int32_t target_cells, int32_t max_cells, int32_t forced_G, int32_t* gdim, void* stream);
+int gsr_knn_cells_axes(const float* points, int32_t N, const float* bbox, const int32_t* gdim, int32_t* cell, void* stream);
+int gsr_knn_mean_dist2_counted(const float* points_sorted, int32_t N, const float* bbox, const int32_t* gdim,
+                               const int32_t* cell_start, float* out, uint32_t* work, void* stream);
 
 #ifdef __cplusplus
 }
