@@ -152,6 +152,9 @@ class GdrTsdfArgs(C.Structure):   # include/gdr.h gdr_tsdf_args
 GDR_ATTN_MAX_SEQLEN = 256
 GDR_ATTN_F16, GDR_ATTN_BF16 = 0, 1
 GDR_ATTN_HEAD_DIMS = (8, 16, 32, 64)
+GDR_SERIAL_ORDERS = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
+GDR_SERIAL_MAX_ORDERS, GDR_SERIAL_MAX_DEPTH, GDR_SERIAL_MAX_POINTS = 8, 16, 1 << 30
+GDR_SERIAL_SORT_TILE, GDR_SERIAL_MAX_SEGMENTS = 1024, 1024
 
 
 class GdrAttnArgs(C.Structure):   # include/gdr.h gdr_attn_args
@@ -278,6 +281,14 @@ _PROTOS = {
                                    C.c_void_p]),
     "gdr_attn_backward": (C.c_int, [C.POINTER(GdrAttnArgs), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_serial_encode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "gdr_serial_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_serial_sort_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "gdr_serial_sort": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "gdr_serial_patch_tables": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

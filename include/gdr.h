@@ -649,6 +649,47 @@ int gdr_attn_backward(const gdr_attn_args* a, const void* dout, const int64_t* d
                       const int64_t* qkv_strides, const int32_t* cu_seqlens, const void* out, const float* lse, void* dqkv,
                       void* stream);
 
+/* ---- point serialization for the point decoder (csrc/serialize.hip; added in v17, backward-compatible) ------------------
+ * What the reference's Point.serialization and SerializedAttention.get_padding_and_inverse compute with tensor ops: the
+ * space-filling-curve code of every point's grid cell under up to GDR_SERIAL_MAX_ORDERS orders, the stable argsort of each
+ * code row with its inverse permutation, and the pad / unpad / cu_seqlens tables of the patch attention.  The code
+ * semantics are restated in the header of csrc/serialize.hip.  The caller owns every buffer; all of them are device memory
+ * except `strides` and `orders`.  Refusals happen before any launch; no entry point synchronises with the host.
+ *
+ * encode: grid_coord (N, 3) int32 or int64 read through its two element strides; batch: N dense int64 or NULL; code: (k, N)
+ *   dense int64, row r under orders[r] (any of the four, repeats allowed).  1 <= depth <= 16; coordinates are taken modulo
+ *   2^depth.  One launch.
+ * decode: order GDR_SERIAL_Z or GDR_SERIAL_HILBERT; code: N dense int64 -> grid_coord (N, 3) dense int64 and batch
+ *   (= code >> 3 * depth), N dense int64.
+ * sort: least-significant-digit radix sort of the k rows of `code` on their `bits` low bits (1..63; higher bits must be
+ *   equal within a row), 32-bit indices inside.  order, inverse: (k, N) dense int64 with code[r, order[r, j]] non-decreasing
+ *   in j, equal codes in ascending point index, and inverse[r, order[r, j]] = j.  workspace: gdr_serial_sort_bytes(k, N)
+ *   bytes, 256-byte aligned.  3 * ceil(bits / 8) launches.
+ * patch_tables: offset: the B segment ends off_1 <= ... <= off_B (off_0 = 0 is implied), patch size P.  Segment i has n_i
+ *   points and the padded length m_i = n_i if n_i <= P, else ceil(n_i / P) * P; poff is the exclusive prefix sum of the m_i.
+ *   unpad[j] = j + poff_i - off_i for point j of segment i; pad[t] = off_i + (l if l < n_i else l - P), l = t - poff_i, for
+ *   padded slot t of segment i; cu_seqlens = for every i the values poff_i, poff_i + P, ... below poff_(i+1), then the padded
+ *   total.  The caller gives the sizes of its buffers — N = off_B entries of unpad, `total` entries of pad, n_seq + 1 entries
+ *   of cu_seqlens — and nothing is written beyond them whatever the offsets on the device say.  One launch. */
+#define GDR_SERIAL_Z 0
+#define GDR_SERIAL_Z_TRANS 1
+#define GDR_SERIAL_HILBERT 2
+#define GDR_SERIAL_HILBERT_TRANS 3
+#define GDR_SERIAL_MAX_ORDERS 8
+#define GDR_SERIAL_MAX_DEPTH 16
+#define GDR_SERIAL_MAX_POINTS (1 << 30)
+#define GDR_SERIAL_SORT_TILE 1024      /* keys per workgroup of the sort */
+#define GDR_SERIAL_MAX_SEGMENTS 1024
+int gdr_serial_encode(const void* grid_coord, const int64_t* strides, int32_t coord_is_int64, const int64_t* batch, int64_t N,
+                      int32_t depth, int32_t k, const int32_t* orders, int64_t* code, void* stream);
+int gdr_serial_decode(const int64_t* code, int64_t N, int32_t depth, int32_t order, int64_t* grid_coord, int64_t* batch,
+                      void* stream);
+size_t gdr_serial_sort_bytes(int32_t k, int64_t N);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_serial_sort(const int64_t* code, int32_t k, int64_t N, int32_t bits, void* workspace, size_t workspace_bytes,
+                    int64_t* order, int64_t* inverse, void* stream);
+int gdr_serial_patch_tables(const int64_t* offset, int32_t B, int32_t P, int64_t N, int64_t total, int32_t n_seq, int64_t* pad,
+                            int64_t* unpad, int32_t* cu_seqlens, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
