@@ -163,6 +163,14 @@ class GdrAttnArgs(C.Structure):   # include/gdr.h gdr_attn_args
                 ("reserved2", C.c_float)]
 
 
+GDR_PF_MAX_VIEWS, GDR_PF_MAX_CHANNELS, GDR_PF_MAX_SIDE, GDR_PF_MAX_POINTS = 16, 4096, 16384, (1 << 31) - 1
+
+
+class GdrPointfeatArgs(C.Structure):   # include/gdr.h gdr_pointfeat_args
+    _fields_ = [("N", C.c_int64), ("V", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # every symbol include/gdr.h and include/gsr.h declare, with its prototype
 _PROTOS = {
     "gdr_abi_version": (C.c_int, []),
@@ -289,6 +297,14 @@ _PROTOS = {
                                   C.c_void_p]),
     "gdr_serial_patch_tables": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_point_feats_forward": (C.c_int, [C.POINTER(GdrPointfeatArgs)] + [C.c_void_p, C.POINTER(C.c_int64)] * 5
+                                + [C.c_void_p] * 4),
+    "gdr_point_feats_backward": (C.c_int, [C.POINTER(GdrPointfeatArgs), C.c_void_p] + [C.c_void_p, C.POINTER(C.c_int64)] * 5
+                                 + [C.c_void_p] * 8),
+    "gdr_sample_views_forward": (C.c_int, [C.POINTER(GdrPointfeatArgs)] + [C.c_void_p, C.POINTER(C.c_int64)] * 2
+                                 + [C.c_void_p] * 5),
+    "gdr_sample_views_backward": (C.c_int, [C.POINTER(GdrPointfeatArgs), C.c_void_p, C.c_void_p]
+                                  + [C.c_void_p, C.POINTER(C.c_int64)] * 2 + [C.c_void_p] * 5),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

@@ -690,6 +690,48 @@ int gdr_serial_sort(const int64_t* code, int32_t k, int64_t N, int32_t bits, voi
 int gdr_serial_patch_tables(const int64_t* offset, int32_t B, int32_t P, int64_t N, int64_t total, int32_t n_seq, int64_t* pad,
                             int64_t* unpad, int32_t* cu_seqlens, void* stream);
 
+/* ---- projected bilinear sampling of point and volume features (csrc/pointfeat.hip; added in v17, backward-compatible) -----
+ * What the reference's Network.get_point_feats and Network.build_feat_vol compute with tensor ops (projection, cat, einsum,
+ * F.grid_sample with zero padding, |depth sample - z|); the arithmetic is restated in the header of csrc/pointfeat.hip.
+ * fp32 only.  The caller owns every buffer; all are device memory except `a` and the stride arrays (int64 element strides,
+ * one per dimension of the tensor they follow).  w2cs (V, 4, 4) and ixts (V, 3, 3) are dense and receive no gradient.
+ * Refusals happen before any launch; N = 0 returns GDR_OK without one; no entry point synchronises with the host.
+ *
+ * point_feats: img_ref (V, 3, H, W), image (V, H, W, 3), acc_map (V, H, W), depth (V, H, W[, 1]: three strides), points
+ *   (N, 3); out (N, V, 8) dense, 16-byte aligned: ref rgb, render rgb, acc, |depth sample - z|.  One launch.
+ * point_feats backward: grad_out (N, V, 8) dense.  grad_img_ref / grad_image / grad_acc_map / grad_depth: dense tensors of
+ *   the sources' shapes that the caller ZERO-FILLED (float atomics add into them); grad_points (N, 3) dense, written with
+ *   plain stores (bitwise reproducible).  A NULL gradient pointer means "not wanted": nothing is issued for it, and a source
+ *   whose values no wanted gradient needs may be NULL too (img_ref, image and acc_map unless grad_points is given).
+ * sample_views: images (V, C, H, W), points (N, 3); out (V, C, N) and z (V, N) dense.  One launch.
+ * sample_views backward: grad_out (V, C, N) dense, grad_z (V, N) dense or NULL (= zeros); grad_images (V, C, H, W) dense and
+ *   zero-filled by the caller, grad_points (N, 3) dense; NULL = not wanted, as above.  One launch. */
+#define GDR_PF_MAX_VIEWS 16
+#define GDR_PF_MAX_CHANNELS 4096
+#define GDR_PF_MAX_SIDE 16384
+#define GDR_PF_MAX_POINTS INT64_C(0x7fffffff)
+typedef struct gdr_pointfeat_args {
+    int64_t N;               /* points */
+    int32_t V, C, H, W;      /* views, channels (sample_views only), image size */
+    int32_t reserved;
+} gdr_pointfeat_args;
+int gdr_point_feats_forward(const gdr_pointfeat_args* a, const float* img_ref, const int64_t* img_ref_strides, const float* image,
+                            const int64_t* image_strides, const float* acc_map, const int64_t* acc_map_strides,
+                            const float* depth, const int64_t* depth_strides, const float* points, const int64_t* points_strides,
+                            const float* w2cs, const float* ixts, float* out, void* stream);
+int gdr_point_feats_backward(const gdr_pointfeat_args* a, const float* grad_out, const float* img_ref,
+                             const int64_t* img_ref_strides, const float* image, const int64_t* image_strides,
+                             const float* acc_map, const int64_t* acc_map_strides, const float* depth,
+                             const int64_t* depth_strides, const float* points, const int64_t* points_strides, const float* w2cs,
+                             const float* ixts, float* grad_img_ref, float* grad_image, float* grad_acc_map, float* grad_depth,
+                             float* grad_points, void* stream);
+int gdr_sample_views_forward(const gdr_pointfeat_args* a, const float* images, const int64_t* images_strides, const float* points,
+                             const int64_t* points_strides, const float* w2cs, const float* ixts, float* out, float* z,
+                             void* stream);
+int gdr_sample_views_backward(const gdr_pointfeat_args* a, const float* grad_out, const float* grad_z, const float* images,
+                              const int64_t* images_strides, const float* points, const int64_t* points_strides,
+                              const float* w2cs, const float* ixts, float* grad_images, float* grad_points, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
