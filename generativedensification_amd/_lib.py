@@ -171,6 +171,15 @@ class GdrPointfeatArgs(C.Structure):   # include/gdr.h gdr_pointfeat_args
                 ("reserved", C.c_int32)]
 
 
+GDR_SUBM_DTYPES = {"f16": 0, "bf16": 1, "f32": 2}
+GDR_SUBM_MAX_TAPS, GDR_SUBM_MAX_CHANNELS, GDR_SUBM_MAX_POINTS = 125, 512, 1 << 30
+
+
+class GdrSubmArgs(C.Structure):   # include/gdr.h gdr_subm_args
+    _fields_ = [("N", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("K", C.c_int32), ("dtype", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # every symbol include/gdr.h and include/gsr.h declare, with its prototype
 _PROTOS = {
     "gdr_abi_version": (C.c_int, []),
@@ -305,6 +314,13 @@ _PROTOS = {
                                  + [C.c_void_p] * 5),
     "gdr_sample_views_backward": (C.c_int, [C.POINTER(GdrPointfeatArgs), C.c_void_p, C.c_void_p]
                                   + [C.c_void_p, C.POINTER(C.c_int64)] * 2 + [C.c_void_p] * 5),
+    "gdr_subm_table_bytes": (C.c_size_t, [C.c_int64]),
+    "gdr_subm_build_table": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_void_p,
+                                       C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_subm_conv_forward": (C.c_int, [C.POINTER(GdrSubmArgs), C.c_void_p, C.c_int64] + [C.c_void_p] * 5),
+    "gdr_subm_backward_bytes": (C.c_size_t, [C.POINTER(GdrSubmArgs)]),
+    "gdr_subm_conv_backward": (C.c_int, [C.POINTER(GdrSubmArgs), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5
+                               + [C.c_size_t] + [C.c_void_p] * 4),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

@@ -732,6 +732,50 @@ int gdr_sample_views_backward(const gdr_pointfeat_args* a, const float* grad_out
                               const int64_t* images_strides, const float* points, const int64_t* points_strides,
                               const float* w2cs, const float* ixts, float* grad_images, float* grad_points, void* stream);
 
+/* ---- submanifold sparse 3-D convolution (csrc/subm_conv.hip; added in v17, backward-compatible) ---------------------------
+ * The one spconv layer of the reference's point decoder (spconv.SubMConv3d, stride 1): a neighbour table per (coordinates,
+ * kernel size), then out[i] = bias + sum_k feat[nbr[k, i]] @ W[k] and its three gradients.  The semantics are restated in the
+ * header of csrc/subm_conv.hip.  The caller owns every buffer; all are device memory except `a`, `spatial_shape` and `ksize`.
+ * Refusals happen before any launch; N = 0 returns GDR_OK without one; no entry point synchronises with the host.
+ *
+ * build_table: indices (N, 4) int32 dense, 16-byte aligned: (batch, c0, c1, c2).  spatial_shape[3] >= 1, batch_size >= 1,
+ *   ksize[3] each 1, 3 or 5: K = ksize[0] * ksize[1] * ksize[2] <= GDR_SUBM_MAX_TAPS taps, tap k = (t0 * ksize[1] + t1) *
+ *   ksize[2] + t2.  nbr (K, N) int32: nbr[k, i] = the site at coord_i + (t0, t1, t2) - ksize / 2 in site i's batch, or -1.
+ *   Sites that share a voxel: a lookup answers the LOWEST point index among them; rep (N) int32 is that index for site i's own
+ *   voxel.  A site with batch >= batch_size or a coordinate outside spatial_shape is never found, has nbr[., i] = -1 and
+ *   rep[i] = i; nothing is read or written out of bounds whatever `indices` holds.  order (N) int32: the sites by ascending
+ *   voxel key ((b S0 + c0) S1 + c1) S2 + c2, equal keys by ascending point index (the runs the backward sums over).
+ *   workspace: gdr_subm_table_bytes(N), 256-byte aligned.  2 launches + gdr_serial_sort on the key's bits; every device
+ *   loop has a trip count the host knows (ceil(log2 N) + 1 search steps).
+ * forward: feat (N, Cin) through its row stride (elements; channels unit-stride), weight (Cout, k0, k1, k2, Cin) dense and
+ *   16-byte aligned (spconv 2.x's parameter layout), bias (Cout) or NULL, out (N, Cout) dense and 16-byte aligned; all of
+ *   a->dtype.  Cross-correlation, f32 accumulation (MFMA), one launch, no atomics: two runs are bitwise equal.
+ * backward: grad_out (N, Cout) dense of a->dtype.  grad_feat (N, Cin) dense of a->dtype; grad_weight (Cout, K, Cin) and
+ *   grad_bias (Cout) dense f32.  A NULL output pointer means "not wanted": nothing is issued for it.  With G = the sum of
+ *   grad_out over each voxel's sites, kept at the representative: grad_feat[j] = sum_k G[nbr[K-1-k, j]] @ W[k]^T for
+ *   representatives and zero rows for the rest, grad_weight[k] = sum_r feat[nbr[k, r]]^T @ G[r], grad_bias = column sums of
+ *   grad_out.  workspace: gdr_subm_backward_bytes(a), 256-byte aligned.  No atomics: two runs are bitwise equal.
+ * Envelope: Cin, Cout multiples of 8 in 8..GDR_SUBM_MAX_CHANNELS, 0 <= N <= GDR_SUBM_MAX_POINTS (the sort's limit). */
+#define GDR_SUBM_F16 0
+#define GDR_SUBM_BF16 1
+#define GDR_SUBM_F32 2
+#define GDR_SUBM_MAX_TAPS 125
+#define GDR_SUBM_MAX_CHANNELS 512
+#define GDR_SUBM_MAX_POINTS (1 << 30)
+typedef struct gdr_subm_args {
+    int32_t N, Cin, Cout, K;     /* sites, channels, taps */
+    int32_t dtype, reserved;     /* GDR_SUBM_F16 / GDR_SUBM_BF16 / GDR_SUBM_F32 */
+} gdr_subm_args;
+size_t gdr_subm_table_bytes(int64_t N);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_subm_build_table(const int32_t* indices, int64_t N, const int32_t* spatial_shape, int32_t batch_size, const int32_t* ksize,
+                         void* workspace, size_t workspace_bytes, int32_t* nbr, int32_t* rep, int32_t* order, void* stream);
+int gdr_subm_conv_forward(const gdr_subm_args* a, const void* feat, int64_t feat_stride, const int32_t* nbr, const void* weight,
+                          const void* bias, void* out, void* stream);
+size_t gdr_subm_backward_bytes(const gdr_subm_args* a);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_subm_conv_backward(const gdr_subm_args* a, const void* grad_out, const void* feat, int64_t feat_stride, const int32_t* nbr,
+                           const int32_t* rep, const int32_t* order, const void* weight, void* workspace, size_t workspace_bytes,
+                           void* grad_feat, float* grad_weight, float* grad_bias, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
