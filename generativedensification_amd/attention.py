@@ -16,16 +16,13 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import _marshal as M
 
 __all__ = ["attn_varlen_qkvpacked", "attn_qkvpacked", "MAX_SEQLEN", "HEAD_DIMS"]
 
 MAX_SEQLEN = L.GDR_ATTN_MAX_SEQLEN
 HEAD_DIMS = L.GDR_ATTN_HEAD_DIMS
 _DTYPES = {torch.float16: L.GDR_ATTN_F16, torch.bfloat16: L.GDR_ATTN_BF16}
-
-
-def _strides(t: torch.Tensor):
-    return (C.c_int64 * t.dim())(*t.stride())
 
 
 class _AttnFunction(torch.autograd.Function):
@@ -40,8 +37,8 @@ class _AttnFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             out = torch.empty(args.total, args.H, args.D, dtype=qkv.dtype, device=dev)
             lse = torch.empty(args.H, args.total, dtype=torch.float32, device=dev)
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            L.check(lib.gdr_attn_forward(C.byref(args), qkv.data_ptr(), _strides(qkv),
+            st = M.stream()
+            L.check(lib.gdr_attn_forward(C.byref(args), qkv.data_ptr(), M.strides(qkv),
                                          None if cu_seqlens is None else cu_seqlens.data_ptr(), out.data_ptr(),
                                          lse.data_ptr(), st), "gdr_attn_forward")
         ctx.save_for_backward(qkv, cu_seqlens, out, lse)
@@ -58,8 +55,8 @@ class _AttnFunction(torch.autograd.Function):
         dout = dout.to(qkv.dtype)
         with torch.cuda.device(dev):
             dqkv = torch.empty(args.total, 3, args.H, args.D, dtype=qkv.dtype, device=dev)
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            L.check(lib.gdr_attn_backward(C.byref(args), dout.data_ptr(), _strides(dout), qkv.data_ptr(), _strides(qkv),
+            st = M.stream()
+            L.check(lib.gdr_attn_backward(C.byref(args), dout.data_ptr(), M.strides(dout), qkv.data_ptr(), M.strides(qkv),
                                           None if cu_seqlens is None else cu_seqlens.data_ptr(), out.data_ptr(),
                                           lse.data_ptr(), dqkv.data_ptr(), st), "gdr_attn_backward")
         return dqkv, None, None

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "gdr_common.h"
+#include "host_util.h"
 
 namespace gdr {
 
@@ -56,8 +57,6 @@ void prof_end(int id, hipStream_t st) {
     g_prof_pending.push_back({id, g_prof_open, b});
     g_prof_open = nullptr;
 }
-
-static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
 // ---- which K7 for a scene shape: rows, or row pairs where they pay (render.hip: render_bwd_pairs_kernel) ---------------
 // K7 is bound by the device's float-atomic line rate wherever the Gaussians span several 4x4 blocks; merging the two rows of

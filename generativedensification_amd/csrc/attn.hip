@@ -29,6 +29,8 @@
 #include <type_traits>
 
 #include "gdr_common.h"
+#include "half_bits.h"
+#include "host_util.h"
 
 namespace gdr {
 namespace {
@@ -48,24 +50,6 @@ struct AttnP {
     int32_t qkv_vec, dout_vec;   // rows are unit-stride and 16-byte aligned: 128-bit loads
     float scale;
 };
-
-template <bool BF>
-__device__ __forceinline__ float up16(uint16_t b) {
-    if constexpr (BF) return __uint_as_float((uint32_t)b << 16);
-    else return (float)__builtin_bit_cast(_Float16, b);
-}
-
-template <bool BF>
-__device__ __forceinline__ uint16_t down16(float f) {   // round to nearest even
-    if constexpr (BF) {
-        uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (uint16_t)(u >> 16);
-    } else {
-        return __builtin_bit_cast(uint16_t, (_Float16)f);
-    }
-}
 
 template <bool BF>
 __device__ __forceinline__ void unpack8(const uint4 w, float* x) {
@@ -341,11 +325,6 @@ __global__ __launch_bounds__(AT_BLOCK) void attn_bwd_kernel(const AttnP p) {
     store_row<D, BF>(p.dqkv + ((tok * 3 + 2) * p.H + h) * D, dv);
 }
 
-int attn_bad(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_INVALID_ARG;
-}
-
 // NULL if the arguments are inside the envelope
 const char* attn_check(const gdr_attn_args* a) {
     if (!a) return "attn: NULL arguments";
@@ -402,10 +381,7 @@ int attn_launch(const gdr_attn_args* a, const AttnP& p, hipStream_t st) {
         default: GDR_ATTN_D(64); break;
     }
 #undef GDR_ATTN_D
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GDR_OK;
-    set_error(BWD ? "attn_bwd_kernel" : "attn_fwd_kernel", e);
-    return GDR_ERR_HIP;
+    return launch_status(BWD ? "attn_bwd_kernel" : "attn_fwd_kernel");
 }
 
 }  // namespace
@@ -416,18 +392,18 @@ using namespace gdr;
 extern "C" {
 
 size_t gdr_attn_lse_bytes(const gdr_attn_args* a) {
-    if (const char* why = attn_check(a)) { attn_bad(why); return 0; }
+    if (const char* why = attn_check(a)) { invalid_arg(why); return 0; }
     return (size_t)a->H * (size_t)a->total * sizeof(float);
 }
 
 int gdr_attn_forward(const gdr_attn_args* a, const void* qkv, const int64_t* qkv_strides, const int32_t* cu_seqlens,
                      void* out, float* lse, void* stream) {
-    if (const char* why = attn_check(a)) return attn_bad(why);
-    if (const char* why = attn_check_fixed(a, cu_seqlens)) return attn_bad(why);
-    if (!qkv_strides) return attn_bad("attn_forward: NULL strides");
+    if (const char* why = attn_check(a)) return invalid_arg(why);
+    if (const char* why = attn_check_fixed(a, cu_seqlens)) return invalid_arg(why);
+    if (!qkv_strides) return invalid_arg("attn_forward: NULL strides");
     if (a->total == 0) return GDR_OK;
-    if (!qkv || !out || !lse) return attn_bad("attn_forward: NULL argument");
-    if (((uintptr_t)out & 15u) || ((uintptr_t)lse & 3u) || ((uintptr_t)qkv & 1u)) return attn_bad("attn_forward: unaligned buffer");
+    if (!qkv || !out || !lse) return invalid_arg("attn_forward: NULL argument");
+    if (misaligned(out, 15) || misaligned(lse, 3) || misaligned(qkv, 1)) return invalid_arg("attn_forward: unaligned buffer");
     AttnP p = {};
     p.qkv = (const uint16_t*)qkv; p.cu = cu_seqlens; p.out = (uint16_t*)out; p.lse = lse;
     p.q0 = qkv_strides[0]; p.q1 = qkv_strides[1]; p.q2 = qkv_strides[2]; p.q3 = qkv_strides[3];
@@ -440,14 +416,13 @@ int gdr_attn_forward(const gdr_attn_args* a, const void* qkv, const int64_t* qkv
 int gdr_attn_backward(const gdr_attn_args* a, const void* dout, const int64_t* dout_strides, const void* qkv,
                       const int64_t* qkv_strides, const int32_t* cu_seqlens, const void* out, const float* lse, void* dqkv,
                       void* stream) {
-    if (const char* why = attn_check(a)) return attn_bad(why);
-    if (const char* why = attn_check_fixed(a, cu_seqlens)) return attn_bad(why);
-    if (!qkv_strides || !dout_strides) return attn_bad("attn_backward: NULL strides");
+    if (const char* why = attn_check(a)) return invalid_arg(why);
+    if (const char* why = attn_check_fixed(a, cu_seqlens)) return invalid_arg(why);
+    if (!qkv_strides || !dout_strides) return invalid_arg("attn_backward: NULL strides");
     if (a->total == 0) return GDR_OK;
-    if (!dout || !qkv || !out || !lse || !dqkv) return attn_bad("attn_backward: NULL argument");
-    if (((uintptr_t)out & 15u) || ((uintptr_t)dqkv & 15u) || ((uintptr_t)lse & 3u) || ((uintptr_t)qkv & 1u) ||
-        ((uintptr_t)dout & 1u))
-        return attn_bad("attn_backward: unaligned buffer");
+    if (!dout || !qkv || !out || !lse || !dqkv) return invalid_arg("attn_backward: NULL argument");
+    if (misaligned(out, 15) || misaligned(dqkv, 15) || misaligned(lse, 3) || misaligned(qkv, 1) || misaligned(dout, 1))
+        return invalid_arg("attn_backward: unaligned buffer");
     AttnP p = {};
     p.qkv = (const uint16_t*)qkv; p.cu = cu_seqlens; p.out = (uint16_t*)out; p.lse = (float*)lse;
     p.dout = (const uint16_t*)dout; p.dqkv = (uint16_t*)dqkv;

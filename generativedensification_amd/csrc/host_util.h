@@ -1,0 +1,32 @@
+// host_util.h — the host-side helpers every module's extern "C" section shares (internal, host only; include after
+// gdr_common.h).  The error text of a call is set_error's (api.hip); these pair it with the status the entry point returns.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace gdr {
+
+static inline int invalid_arg(const char* what) {
+    set_error(what, hipSuccess);
+    return GDR_ERR_INVALID_ARG;
+}
+
+// the status of the launches an entry point has just issued; `what` names the kernel
+static inline int launch_status(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return GDR_OK;
+    set_error(what, e);
+    return GDR_ERR_HIP;
+}
+
+static inline int workspace_too_small(const char* what) {
+    set_error(what, hipSuccess);
+    return GDR_ERR_WORKSPACE;
+}
+
+static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+// mask = alignment in bytes - 1; a NULL pointer is aligned
+static inline bool misaligned(const void* p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
+
+}  // namespace gdr

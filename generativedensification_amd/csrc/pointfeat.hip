@@ -22,6 +22,7 @@
 //   one thread and written with plain stores: bitwise reproducible.  With the point gradient wanted a thread owns a point and
 //   walks every view; sample_views without it spreads views and channel blocks over the grid like the forward.
 #include "gdr_common.h"
+#include "host_util.h"
 
 namespace gdr {
 namespace {
@@ -297,18 +298,6 @@ __global__ __launch_bounds__(PF_BLOCK) void sample_views_bwd_kernel(const ViewsP
     }
 }
 
-int pf_bad(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_INVALID_ARG;
-}
-
-int pf_done(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GDR_OK;
-    set_error(what, e);
-    return GDR_ERR_HIP;
-}
-
 const char* pf_check(const gdr_pointfeat_args* a, bool channels) {
     if (!a) return "pointfeat: NULL args";
     if (a->N < 0 || a->N > GDR_PF_MAX_POINTS) return "pointfeat: N must be in 0..2^31-1";
@@ -317,8 +306,6 @@ const char* pf_check(const gdr_pointfeat_args* a, bool channels) {
     if (channels && (a->C < 1 || a->C > GDR_PF_MAX_CHANNELS)) return "pointfeat: C must be in 1..GDR_PF_MAX_CHANNELS";
     return nullptr;
 }
-
-bool misaligned(const void* p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
 
 }  // namespace
 }  // namespace gdr
@@ -331,15 +318,15 @@ int gdr_point_feats_forward(const gdr_pointfeat_args* a, const float* img_ref, c
                             const int64_t* image_strides, const float* acc_map, const int64_t* acc_map_strides,
                             const float* depth, const int64_t* depth_strides, const float* points, const int64_t* points_strides,
                             const float* w2cs, const float* ixts, float* out, void* stream) {
-    if (const char* why = pf_check(a, false)) return pf_bad(why);
+    if (const char* why = pf_check(a, false)) return invalid_arg(why);
     if (!img_ref_strides || !image_strides || !acc_map_strides || !depth_strides || !points_strides)
-        return pf_bad("point_feats_forward: NULL strides");
+        return invalid_arg("point_feats_forward: NULL strides");
     if (a->N == 0) return GDR_OK;
     if (!img_ref || !image || !acc_map || !depth || !points || !w2cs || !ixts || !out)
-        return pf_bad("point_feats_forward: NULL argument");
+        return invalid_arg("point_feats_forward: NULL argument");
     if (misaligned(img_ref, 3) || misaligned(image, 3) || misaligned(acc_map, 3) || misaligned(depth, 3) || misaligned(points, 3) ||
         misaligned(w2cs, 3) || misaligned(ixts, 3) || misaligned(out, 15))
-        return pf_bad("point_feats_forward: unaligned buffer (out needs 16 bytes)");
+        return invalid_arg("point_feats_forward: unaligned buffer (out needs 16 bytes)");
     FeatP p = {};
     p.ref = img_ref; p.img = image; p.acc = acc_map; p.dep = depth; p.pts = points; p.w2c = w2cs; p.ixt = ixts; p.out = out;
     for (int i = 0; i < 4; ++i) { p.ref_s[i] = img_ref_strides[i]; p.img_s[i] = image_strides[i]; }
@@ -347,7 +334,7 @@ int gdr_point_feats_forward(const gdr_pointfeat_args* a, const float* img_ref, c
     p.pts_s[0] = points_strides[0]; p.pts_s[1] = points_strides[1];
     p.N = a->N; p.V = a->V; p.H = a->H; p.W = a->W;
     hipLaunchKernelGGL(point_feats_fwd_kernel, dim3(div_up(a->N * a->V, PF_BLOCK)), dim3(PF_BLOCK), 0, (hipStream_t)stream, p);
-    return pf_done("point_feats_fwd_kernel");
+    return launch_status("point_feats_fwd_kernel");
 }
 
 int gdr_point_feats_backward(const gdr_pointfeat_args* a, const float* grad_out, const float* img_ref,
@@ -356,17 +343,18 @@ int gdr_point_feats_backward(const gdr_pointfeat_args* a, const float* grad_out,
                              const int64_t* depth_strides, const float* points, const int64_t* points_strides, const float* w2cs,
                              const float* ixts, float* grad_img_ref, float* grad_image, float* grad_acc_map, float* grad_depth,
                              float* grad_points, void* stream) {
-    if (const char* why = pf_check(a, false)) return pf_bad(why);
+    if (const char* why = pf_check(a, false)) return invalid_arg(why);
     if (!img_ref_strides || !image_strides || !acc_map_strides || !depth_strides || !points_strides)
-        return pf_bad("point_feats_backward: NULL strides");
+        return invalid_arg("point_feats_backward: NULL strides");
     if (a->N == 0) return GDR_OK;
     if (!grad_img_ref && !grad_image && !grad_acc_map && !grad_depth && !grad_points) return GDR_OK;   // nothing is wanted
-    if (!grad_out || !depth || !points || !w2cs || !ixts) return pf_bad("point_feats_backward: NULL argument");
-    if (grad_points && (!img_ref || !image || !acc_map)) return pf_bad("point_feats_backward: the point gradient reads every source");
+    if (!grad_out || !depth || !points || !w2cs || !ixts) return invalid_arg("point_feats_backward: NULL argument");
+    if (grad_points && (!img_ref || !image || !acc_map))
+        return invalid_arg("point_feats_backward: the point gradient reads every source");
     if (misaligned(grad_out, 3) || misaligned(img_ref, 3) || misaligned(image, 3) || misaligned(acc_map, 3) || misaligned(depth, 3) ||
         misaligned(points, 3) || misaligned(w2cs, 3) || misaligned(ixts, 3) || misaligned(grad_img_ref, 3) ||
         misaligned(grad_image, 3) || misaligned(grad_acc_map, 3) || misaligned(grad_depth, 3) || misaligned(grad_points, 3))
-        return pf_bad("point_feats_backward: unaligned buffer");
+        return invalid_arg("point_feats_backward: unaligned buffer");
     FeatP p = {};
     p.ref = img_ref; p.img = image; p.acc = acc_map; p.dep = depth; p.pts = points; p.w2c = w2cs; p.ixt = ixts; p.gout = grad_out;
     p.g_ref = grad_img_ref; p.g_img = grad_image; p.g_acc = grad_acc_map; p.g_dep = grad_depth; p.g_pts = grad_points;
@@ -375,19 +363,19 @@ int gdr_point_feats_backward(const gdr_pointfeat_args* a, const float* grad_out,
     p.pts_s[0] = points_strides[0]; p.pts_s[1] = points_strides[1];
     p.N = a->N; p.V = a->V; p.H = a->H; p.W = a->W;
     hipLaunchKernelGGL(point_feats_bwd_kernel, dim3(div_up(a->N, PF_BLOCK)), dim3(PF_BLOCK), 0, (hipStream_t)stream, p);
-    return pf_done("point_feats_bwd_kernel");
+    return launch_status("point_feats_bwd_kernel");
 }
 
 int gdr_sample_views_forward(const gdr_pointfeat_args* a, const float* images, const int64_t* images_strides, const float* points,
                              const int64_t* points_strides, const float* w2cs, const float* ixts, float* out, float* z,
                              void* stream) {
-    if (const char* why = pf_check(a, true)) return pf_bad(why);
-    if (!images_strides || !points_strides) return pf_bad("sample_views_forward: NULL strides");
+    if (const char* why = pf_check(a, true)) return invalid_arg(why);
+    if (!images_strides || !points_strides) return invalid_arg("sample_views_forward: NULL strides");
     if (a->N == 0) return GDR_OK;
-    if (!images || !points || !w2cs || !ixts || !out || !z) return pf_bad("sample_views_forward: NULL argument");
+    if (!images || !points || !w2cs || !ixts || !out || !z) return invalid_arg("sample_views_forward: NULL argument");
     if (misaligned(images, 3) || misaligned(points, 3) || misaligned(w2cs, 3) || misaligned(ixts, 3) || misaligned(out, 3) ||
         misaligned(z, 3))
-        return pf_bad("sample_views_forward: unaligned buffer");
+        return invalid_arg("sample_views_forward: unaligned buffer");
     ViewsP p = {};
     p.img = images; p.pts = points; p.w2c = w2cs; p.ixt = ixts; p.out = out; p.z = z;
     for (int i = 0; i < 4; ++i) p.img_s[i] = images_strides[i];
@@ -396,21 +384,21 @@ int gdr_sample_views_forward(const gdr_pointfeat_args* a, const float* images, c
     p.views_per_row = 1; p.chunk = PF_CHUNK;
     hipLaunchKernelGGL(sample_views_fwd_kernel, dim3(div_up(a->N, PF_BLOCK), a->V, div_up(a->C, PF_CHUNK)), dim3(PF_BLOCK), 0,
                        (hipStream_t)stream, p);
-    return pf_done("sample_views_fwd_kernel");
+    return launch_status("sample_views_fwd_kernel");
 }
 
 int gdr_sample_views_backward(const gdr_pointfeat_args* a, const float* grad_out, const float* grad_z, const float* images,
                               const int64_t* images_strides, const float* points, const int64_t* points_strides,
                               const float* w2cs, const float* ixts, float* grad_images, float* grad_points, void* stream) {
-    if (const char* why = pf_check(a, true)) return pf_bad(why);
-    if (!images_strides || !points_strides) return pf_bad("sample_views_backward: NULL strides");
+    if (const char* why = pf_check(a, true)) return invalid_arg(why);
+    if (!images_strides || !points_strides) return invalid_arg("sample_views_backward: NULL strides");
     if (a->N == 0) return GDR_OK;
     if (!grad_images && !grad_points) return GDR_OK;   // nothing is wanted
-    if (!grad_out || !points || !w2cs || !ixts) return pf_bad("sample_views_backward: NULL argument");
-    if (grad_points && !images) return pf_bad("sample_views_backward: the point gradient reads the images");
+    if (!grad_out || !points || !w2cs || !ixts) return invalid_arg("sample_views_backward: NULL argument");
+    if (grad_points && !images) return invalid_arg("sample_views_backward: the point gradient reads the images");
     if (misaligned(grad_out, 3) || misaligned(grad_z, 3) || misaligned(images, 3) || misaligned(points, 3) || misaligned(w2cs, 3) ||
         misaligned(ixts, 3) || misaligned(grad_images, 3) || misaligned(grad_points, 3))
-        return pf_bad("sample_views_backward: unaligned buffer");
+        return invalid_arg("sample_views_backward: unaligned buffer");
     ViewsP p = {};
     p.img = images; p.pts = points; p.w2c = w2cs; p.ixt = ixts; p.gout = grad_out; p.gz = grad_z;
     p.g_img = grad_images; p.g_pts = grad_points;
@@ -422,7 +410,7 @@ int gdr_sample_views_backward(const gdr_pointfeat_args* a, const float* grad_out
     p.chunk = grad_points ? a->C : PF_CHUNK;
     hipLaunchKernelGGL(sample_views_bwd_kernel, dim3(div_up(a->N, PF_BLOCK), div_up(a->V, p.views_per_row), div_up(a->C, p.chunk)),
                        dim3(PF_BLOCK), 0, (hipStream_t)stream, p);
-    return pf_done("sample_views_bwd_kernel");
+    return launch_status("sample_views_bwd_kernel");
 }
 
 }  // extern "C"

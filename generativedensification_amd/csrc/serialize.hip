@@ -24,6 +24,7 @@
 // Patch tables: one launch.  Every workgroup scans the segment table (B <= 1024) into LDS, then each thread finds the segment
 // of its slot by binary search.  Every write is bounded by the caller's buffer sizes whatever the offsets on the device say.
 #include "gdr_common.h"
+#include "host_util.h"
 #include "serial_bits.h"
 
 namespace gdr {
@@ -241,25 +242,11 @@ __global__ __launch_bounds__(SR_BLOCK) void serial_patch_kernel(const PatchP p) 
     }
 }
 
-int serial_bad(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_INVALID_ARG;
-}
-
-int serial_done(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GDR_OK;
-    set_error(what, e);
-    return GDR_ERR_HIP;
-}
-
 const char* serial_check(int64_t N, int32_t depth) {
     if (N < 0 || N > GDR_SERIAL_MAX_POINTS) return "serial: N must be in 0..GDR_SERIAL_MAX_POINTS";
     if (depth < 1 || depth > GDR_SERIAL_MAX_DEPTH) return "serial: depth must be in 1..16";
     return nullptr;
 }
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct SortWs { size_t keys[2], vals[2], hist, bytes; };
 
@@ -267,9 +254,9 @@ SortWs sort_workspace(int32_t k, int64_t N) {
     SortWs w;
     const size_t kn = (size_t)k * (size_t)N, nblk = ((size_t)N + GDR_SERIAL_SORT_TILE - 1) / GDR_SERIAL_SORT_TILE;
     size_t at = 0;
-    for (int i = 0; i < 2; ++i) { w.keys[i] = at; at += align256(kn * 8); }
-    for (int i = 0; i < 2; ++i) { w.vals[i] = at; at += align256(kn * 4); }
-    w.hist = at; at += align256((size_t)k * SR_RADIX * nblk * 4);
+    for (int i = 0; i < 2; ++i) { w.keys[i] = at; at += align_up(kn * 8); }
+    for (int i = 0; i < 2; ++i) { w.vals[i] = at; at += align_up(kn * 4); }
+    w.hist = at; at += align_up((size_t)k * SR_RADIX * nblk * 4);
     w.bytes = at;
     return w;
 }
@@ -283,40 +270,40 @@ extern "C" {
 
 int gdr_serial_encode(const void* grid_coord, const int64_t* strides, int32_t coord_is_int64, const int64_t* batch, int64_t N,
                       int32_t depth, int32_t k, const int32_t* orders, int64_t* code, void* stream) {
-    if (const char* why = serial_check(N, depth)) return serial_bad(why);
-    if (k < 1 || k > GDR_SERIAL_MAX_ORDERS || !orders) return serial_bad("serial_encode: k must be in 1..GDR_SERIAL_MAX_ORDERS");
-    if (!strides) return serial_bad("serial_encode: NULL strides");
+    if (const char* why = serial_check(N, depth)) return invalid_arg(why);
+    if (k < 1 || k > GDR_SERIAL_MAX_ORDERS || !orders) return invalid_arg("serial_encode: k must be in 1..GDR_SERIAL_MAX_ORDERS");
+    if (!strides) return invalid_arg("serial_encode: NULL strides");
     EncP p = {};
     for (int r = 0; r < k; ++r) {
-        if (orders[r] < GDR_SERIAL_Z || orders[r] > GDR_SERIAL_HILBERT_TRANS) return serial_bad("serial_encode: unknown order");
+        if (orders[r] < GDR_SERIAL_Z || orders[r] > GDR_SERIAL_HILBERT_TRANS) return invalid_arg("serial_encode: unknown order");
         p.ord[r] = orders[r];
     }
     if (N == 0) return GDR_OK;
-    if (!grid_coord || !code) return serial_bad("serial_encode: NULL argument");
-    if (((uintptr_t)grid_coord & (coord_is_int64 ? 7u : 3u)) || ((uintptr_t)code & 7u) || ((uintptr_t)batch & 7u))
-        return serial_bad("serial_encode: unaligned buffer");
+    if (!grid_coord || !code) return invalid_arg("serial_encode: NULL argument");
+    if (misaligned(grid_coord, coord_is_int64 ? 7 : 3) || misaligned(code, 7) || misaligned(batch, 7))
+        return invalid_arg("serial_encode: unaligned buffer");
     p.coord = grid_coord; p.batch = batch; p.code = code; p.s0 = strides[0]; p.s1 = strides[1];
     p.n = (uint32_t)N; p.depth = depth; p.k = k; p.coord64 = coord_is_int64 ? 1 : 0;
     hipLaunchKernelGGL(serial_encode_kernel, dim3(div_up(N, SR_BLOCK)), dim3(SR_BLOCK), 0, (hipStream_t)stream, p);
-    return serial_done("serial_encode_kernel");
+    return launch_status("serial_encode_kernel");
 }
 
 int gdr_serial_decode(const int64_t* code, int64_t N, int32_t depth, int32_t order, int64_t* grid_coord, int64_t* batch,
                       void* stream) {
-    if (const char* why = serial_check(N, depth)) return serial_bad(why);
-    if (order != GDR_SERIAL_Z && order != GDR_SERIAL_HILBERT) return serial_bad("serial_decode: order must be z or hilbert");
+    if (const char* why = serial_check(N, depth)) return invalid_arg(why);
+    if (order != GDR_SERIAL_Z && order != GDR_SERIAL_HILBERT) return invalid_arg("serial_decode: order must be z or hilbert");
     if (N == 0) return GDR_OK;
-    if (!code || !grid_coord || !batch) return serial_bad("serial_decode: NULL argument");
-    if (((uintptr_t)code & 7u) || ((uintptr_t)grid_coord & 7u) || ((uintptr_t)batch & 7u))
-        return serial_bad("serial_decode: unaligned buffer");
+    if (!code || !grid_coord || !batch) return invalid_arg("serial_decode: NULL argument");
+    if (misaligned(code, 7) || misaligned(grid_coord, 7) || misaligned(batch, 7))
+        return invalid_arg("serial_decode: unaligned buffer");
     hipLaunchKernelGGL(serial_decode_kernel, dim3(div_up(N, SR_BLOCK)), dim3(SR_BLOCK), 0, (hipStream_t)stream, code,
                        (uint32_t)N, depth, order == GDR_SERIAL_HILBERT ? 1 : 0, grid_coord, batch);
-    return serial_done("serial_decode_kernel");
+    return launch_status("serial_decode_kernel");
 }
 
 size_t gdr_serial_sort_bytes(int32_t k, int64_t N) {
     if (k < 1 || k > GDR_SERIAL_MAX_ORDERS || N < 0 || N > GDR_SERIAL_MAX_POINTS) {
-        serial_bad("serial_sort_bytes: k or N outside the envelope");
+        invalid_arg("serial_sort_bytes: k or N outside the envelope");
         return 0;
     }
     return sort_workspace(k, N).bytes + 256;   // (never 0 for valid arguments)
@@ -324,18 +311,16 @@ size_t gdr_serial_sort_bytes(int32_t k, int64_t N) {
 
 int gdr_serial_sort(const int64_t* code, int32_t k, int64_t N, int32_t bits, void* workspace, size_t workspace_bytes,
                     int64_t* order, int64_t* inverse, void* stream) {
-    if (k < 1 || k > GDR_SERIAL_MAX_ORDERS) return serial_bad("serial_sort: k must be in 1..GDR_SERIAL_MAX_ORDERS");
-    if (N < 0 || N > GDR_SERIAL_MAX_POINTS) return serial_bad("serial_sort: N must be in 0..GDR_SERIAL_MAX_POINTS");
-    if (bits < 1 || bits > 63) return serial_bad("serial_sort: bits must be in 1..63");
+    if (k < 1 || k > GDR_SERIAL_MAX_ORDERS) return invalid_arg("serial_sort: k must be in 1..GDR_SERIAL_MAX_ORDERS");
+    if (N < 0 || N > GDR_SERIAL_MAX_POINTS) return invalid_arg("serial_sort: N must be in 0..GDR_SERIAL_MAX_POINTS");
+    if (bits < 1 || bits > 63) return invalid_arg("serial_sort: bits must be in 1..63");
     if (N == 0) return GDR_OK;
-    if (!code || !order || !inverse || !workspace) return serial_bad("serial_sort: NULL argument");
-    if (((uintptr_t)code & 7u) || ((uintptr_t)order & 7u) || ((uintptr_t)inverse & 7u) || ((uintptr_t)workspace & 255u))
-        return serial_bad("serial_sort: unaligned buffer");
+    if (!code || !order || !inverse || !workspace) return invalid_arg("serial_sort: NULL argument");
+    if (misaligned(code, 7) || misaligned(order, 7) || misaligned(inverse, 7) || misaligned(workspace, 255))
+        return invalid_arg("serial_sort: unaligned buffer");
     const SortWs ws = sort_workspace(k, N);
-    if (workspace_bytes < ws.bytes) {
-        set_error("serial_sort: workspace smaller than gdr_serial_sort_bytes", hipSuccess);
-        return GDR_ERR_WORKSPACE;
-    }
+    if (workspace_bytes < ws.bytes)
+        return workspace_too_small("serial_sort: workspace smaller than gdr_serial_sort_bytes");
     char* base = (char*)workspace;
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t nblk = (uint32_t)div_up(N, GDR_SERIAL_SORT_TILE);
@@ -355,18 +340,18 @@ int gdr_serial_sort(const int64_t* code, int32_t k, int64_t N, int32_t bits, voi
         hipLaunchKernelGGL(serial_scatter_kernel, grid, dim3(SR_BLOCK), 0, st, p);
         p.kin = p.kout; p.vin = p.vout;
     }
-    return serial_done("serial_sort kernels");
+    return launch_status("serial_sort kernels");
 }
 
 int gdr_serial_patch_tables(const int64_t* offset, int32_t B, int32_t P, int64_t N, int64_t total, int32_t n_seq, int64_t* pad,
                             int64_t* unpad, int32_t* cu_seqlens, void* stream) {
-    if (B < 1 || B > GDR_SERIAL_MAX_SEGMENTS) return serial_bad("serial_patch_tables: B must be in 1..GDR_SERIAL_MAX_SEGMENTS");
-    if (P < 1) return serial_bad("serial_patch_tables: patch size must be >= 1");
+    if (B < 1 || B > GDR_SERIAL_MAX_SEGMENTS) return invalid_arg("serial_patch_tables: B must be in 1..GDR_SERIAL_MAX_SEGMENTS");
+    if (P < 1) return invalid_arg("serial_patch_tables: patch size must be >= 1");
     if (N < 0 || total < N || n_seq < 0 || total > INT64_C(0x7fffffff))
-        return serial_bad("serial_patch_tables: sizes must satisfy 0 <= N <= total < 2^31, n_seq >= 0");
-    if (!offset || !cu_seqlens || (N && !unpad) || (total && !pad)) return serial_bad("serial_patch_tables: NULL argument");
-    if (((uintptr_t)offset & 7u) || ((uintptr_t)pad & 7u) || ((uintptr_t)unpad & 7u) || ((uintptr_t)cu_seqlens & 3u))
-        return serial_bad("serial_patch_tables: unaligned buffer");
+        return invalid_arg("serial_patch_tables: sizes must satisfy 0 <= N <= total < 2^31, n_seq >= 0");
+    if (!offset || !cu_seqlens || (N && !unpad) || (total && !pad)) return invalid_arg("serial_patch_tables: NULL argument");
+    if (misaligned(offset, 7) || misaligned(pad, 7) || misaligned(unpad, 7) || misaligned(cu_seqlens, 3))
+        return invalid_arg("serial_patch_tables: unaligned buffer");
     PatchP p = {};
     p.offset = offset; p.pad = pad; p.unpad = unpad; p.cu = cu_seqlens; p.n = N; p.total = total; p.B = B; p.P = P; p.n_seq = n_seq;
     int64_t work = total > (int64_t)n_seq + 1 ? total : (int64_t)n_seq + 1;
@@ -374,7 +359,7 @@ int gdr_serial_patch_tables(const int64_t* offset, int32_t B, int32_t P, int64_t
     if (blocks < 1) blocks = 1;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(serial_patch_kernel, dim3(blocks), dim3(SR_BLOCK), 0, (hipStream_t)stream, p);
-    return serial_done("serial_patch_kernel");
+    return launch_status("serial_patch_kernel");
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "gdr_common.h"
+#include "host_util.h"
 
 namespace gdr {
 namespace {
@@ -316,8 +317,6 @@ struct SsLayout {
     size_t cmap, gx[GDR_SSIM_MAX_LEVELS], gy[GDR_SSIM_MAX_LEVELS], scratch_bytes;
 };
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 // NULL = valid; otherwise the reason the arguments are refused
 const char* ssim_layout(const gdr_ssim_args* a, int want_dy, SsLayout* o) {
     if (!a) return "NULL args";
@@ -343,7 +342,7 @@ const char* ssim_layout(const gdr_ssim_args* a, int want_dy, SsLayout* o) {
         part += (size_t)o->P * o->lv.tiles[l] * 2;
         o->px[l] = o->py[l] = 0;
         if (l > 0) {
-            const size_t n = align256((size_t)o->P * h * w * sizeof(float));
+            const size_t n = align_up((size_t)o->P * h * w * sizeof(float));
             o->px[l] = off;
             o->py[l] = off + n;
             off += 2 * n;
@@ -352,17 +351,17 @@ const char* ssim_layout(const gdr_ssim_args* a, int want_dy, SsLayout* o) {
         w = (w + (w & 1)) >> 1;
     }
     o->part = off;
-    off += align256(part * sizeof(float));
+    off += align_up(part * sizeof(float));
     o->coef = off;
-    off += align256((size_t)o->P * o->L * sizeof(float));
+    off += align_up((size_t)o->P * o->L * sizeof(float));
     o->ws_bytes = off;
     off = 0;
     o->cmap = off;
-    off += align256((size_t)o->P * (a->H - o->K + 1) * (a->W - o->K + 1) * sizeof(float4));
+    off += align_up((size_t)o->P * (a->H - o->K + 1) * (a->W - o->K + 1) * sizeof(float4));
     for (int l = 0; l < o->L; ++l) {
         o->gx[l] = o->gy[l] = 0;
         if (l == 0) continue;
-        const size_t n = align256((size_t)o->P * o->lv.h[l] * o->lv.w[l] * sizeof(float));
+        const size_t n = align_up((size_t)o->P * o->lv.h[l] * o->lv.w[l] * sizeof(float));
         o->gx[l] = off;
         off += n;
         if (want_dy) {
@@ -405,40 +404,28 @@ SsWin window(const gdr_ssim_args* a) {
         default: CALL(15); break;                                                                                         \
     }
 
-int ssim_bad(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_INVALID_ARG;
-}
-
-int ssim_hip(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GDR_OK;
-    set_error(what, e);
-    return GDR_ERR_HIP;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t gdr_ssim_workspace_bytes(const gdr_ssim_args* a) {
     SsLayout o;
-    if (const char* why = ssim_layout(a, 0, &o)) { ssim_bad(why); return 0; }
+    if (const char* why = ssim_layout(a, 0, &o)) { invalid_arg(why); return 0; }
     return o.ws_bytes;
 }
 
 size_t gdr_ssim_scratch_bytes(const gdr_ssim_args* a, int32_t want_dy) {
     SsLayout o;
-    if (const char* why = ssim_layout(a, want_dy, &o)) { ssim_bad(why); return 0; }
+    if (const char* why = ssim_layout(a, want_dy, &o)) { invalid_arg(why); return 0; }
     return o.scratch_bytes;
 }
 
 int gdr_ssim_forward(const gdr_ssim_args* a, const float* X, const int64_t* x_strides, const float* Y,
                      const int64_t* y_strides, void* workspace, float* out, void* stream) {
     SsLayout o;
-    if (const char* why = ssim_layout(a, 0, &o)) return ssim_bad(why);
-    if (!X || !Y || !x_strides || !y_strides || !workspace || !out) return ssim_bad("ssim_forward: NULL argument");
-    if ((uintptr_t)workspace & 255u) return ssim_bad("ssim_forward: workspace unaligned");
+    if (const char* why = ssim_layout(a, 0, &o)) return invalid_arg(why);
+    if (!X || !Y || !x_strides || !y_strides || !workspace || !out) return invalid_arg("ssim_forward: NULL argument");
+    if (misaligned(workspace, 255)) return invalid_arg("ssim_forward: workspace unaligned");
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     float* part = (float*)(ws + o.part);
@@ -453,14 +440,14 @@ int gdr_ssim_forward(const gdr_ssim_args* a, const float* X, const int64_t* x_st
                        (int)(l == o.L - 1), pl, (const float*)nullptr, (const float*)nullptr, o.L, l, (float4*)nullptr)
         GDR_SSIM_DISPATCH(o.K, GDR_SSIM_FWD)
 #undef GDR_SSIM_FWD
-        if (int rc = ssim_hip("ssim_tile_kernel")) return rc;
+        if (int rc = launch_status("ssim_tile_kernel")) return rc;
         if (l + 1 < o.L) {
             const int h2 = o.lv.h[l + 1], w2 = o.lv.w[l + 1];
             float* nx = (float*)(ws + o.px[l + 1]);
             float* ny = (float*)(ws + o.py[l + 1]);
             const int grid_p = (int)std::min<int64_t>(div_up((int64_t)o.P * h2 * w2, GDR_BLOCK), 8192);
             hipLaunchKernelGGL(ssim_pool_kernel, dim3(grid_p), dim3(GDR_BLOCK), 0, st, x, y, o.P, h, w, nx, ny);
-            if (int rc = ssim_hip("ssim_pool_kernel")) return rc;
+            if (int rc = launch_status("ssim_pool_kernel")) return rc;
             x = dense(nx, h2, w2);
             y = dense(ny, h2, w2);
         }
@@ -469,7 +456,7 @@ int gdr_ssim_forward(const gdr_ssim_args* a, const float* X, const int64_t* x_st
     for (int l = 0; l < o.L; ++l) wts.g[l] = a->weights[l];
     hipLaunchKernelGGL(ssim_finalize_kernel, dim3(o.P), dim3(GDR_BLOCK), 0, st, (const float*)part, o.lv, o.L, a->mode,
                        wts, out, (float*)(ws + o.coef));
-    return ssim_hip("ssim_finalize_kernel");
+    return launch_status("ssim_finalize_kernel");
 }
 
 int gdr_ssim_backward(const gdr_ssim_args* a, const float* X, const int64_t* x_strides, const float* Y,
@@ -477,11 +464,11 @@ int gdr_ssim_backward(const gdr_ssim_args* a, const float* X, const int64_t* x_s
                       const int64_t* dx_strides, float* dY, const int64_t* dy_strides, void* scratch, void* stream) {
     SsLayout o;
     const bool want_dy = dY != nullptr;
-    if (const char* why = ssim_layout(a, want_dy, &o)) return ssim_bad(why);
+    if (const char* why = ssim_layout(a, want_dy, &o)) return invalid_arg(why);
     if (!X || !Y || !x_strides || !y_strides || !workspace || !grad_out || !dX || !dx_strides || !scratch ||
         (want_dy && !dy_strides))
-        return ssim_bad("ssim_backward: NULL argument");
-    if (((uintptr_t)workspace | (uintptr_t)scratch) & 255u) return ssim_bad("ssim_backward: workspace unaligned");
+        return invalid_arg("ssim_backward: NULL argument");
+    if (misaligned(workspace, 255) || misaligned(scratch, 255)) return invalid_arg("ssim_backward: workspace unaligned");
     hipStream_t st = (hipStream_t)stream;
     const char* ws = (const char*)workspace;
     char* sc = (char*)scratch;
@@ -498,7 +485,7 @@ int gdr_ssim_backward(const gdr_ssim_args* a, const float* X, const int64_t* x_s
                        (int)(l == o.L - 1), (float*)nullptr, grad_out, coef, o.L, l, cmap)
         GDR_SSIM_DISPATCH(o.K, GDR_SSIM_COEF)
 #undef GDR_SSIM_COEF
-        if (int rc = ssim_hip("ssim_tile_kernel (backward)")) return rc;
+        if (int rc = launch_status("ssim_tile_kernel (backward)")) return rc;
         const float* dnx = l + 1 < o.L ? (const float*)(sc + o.gx[l + 1]) : nullptr;
         const float* dny = l + 1 < o.L && want_dy ? (const float*)(sc + o.gy[l + 1]) : nullptr;
         SsOut ox, oy;
@@ -526,7 +513,7 @@ int gdr_ssim_backward(const gdr_ssim_args* a, const float* X, const int64_t* x_s
                            (const float4*)cmap, dnx, dny, ox, oy)
         GDR_SSIM_DISPATCH(o.K, GDR_SSIM_GRAD)
 #undef GDR_SSIM_GRAD
-        if (int rc = ssim_hip("ssim_grad_kernel")) return rc;
+        if (int rc = launch_status("ssim_grad_kernel")) return rc;
     }
     return GDR_OK;
 }

@@ -31,6 +31,8 @@
 #include <type_traits>
 
 #include "gdr_common.h"
+#include "half_bits.h"
+#include "host_util.h"
 
 namespace gdr {
 namespace {
@@ -55,18 +57,12 @@ template <int DT> struct El {
 
 template <int DT> __device__ __forceinline__ float up(typename El<DT>::type v) {
     if constexpr (DT == GDR_SUBM_F32) return v;
-    else if constexpr (DT == GDR_SUBM_BF16) return __uint_as_float((uint32_t)v << 16);
-    else return (float)__builtin_bit_cast(_Float16, v);
+    else return up16<DT == GDR_SUBM_BF16>(v);
 }
 
 template <int DT> __device__ __forceinline__ typename El<DT>::type down(float f) {   // round to nearest even
     if constexpr (DT == GDR_SUBM_F32) return f;
-    else if constexpr (DT == GDR_SUBM_BF16) {
-        uint32_t u = __float_as_uint(f);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (uint16_t)(u >> 16);
-    } else return __builtin_bit_cast(uint16_t, (_Float16)f);
+    else return down16<DT == GDR_SUBM_BF16>(f);
 }
 
 // VE elements from global memory as one 16-byte vector (vec) or one by one
@@ -421,20 +417,6 @@ __global__ __launch_bounds__(SC_BLOCK) void subm_gw_kernel(const GwP p) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
-int subm_bad(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_INVALID_ARG;
-}
-
-int subm_done(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GDR_OK;
-    set_error(what, e);
-    return GDR_ERR_HIP;
-}
-
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 const char* subm_check(const gdr_subm_args* a) {
     if (!a) return "subm: NULL arguments";
     if (a->dtype != GDR_SUBM_F16 && a->dtype != GDR_SUBM_BF16 && a->dtype != GDR_SUBM_F32) return "subm: unknown dtype";
@@ -453,9 +435,9 @@ struct BwdWs { size_t G, wt, part, bytes; };
 BwdWs bwd_workspace(const gdr_subm_args* a) {
     BwdWs w;
     size_t at = 0;
-    w.G = at; at += al256((size_t)planes_of(a->dtype) * (size_t)a->N * a->Cout * esize(a->dtype));
-    w.wt = at; at += al256((size_t)a->K * a->Cin * a->Cout * esize(a->dtype));
-    w.part = at; at += al256((size_t)SC_BIAS_BLOCKS * a->Cout * sizeof(float));
+    w.G = at; at += align_up((size_t)planes_of(a->dtype) * (size_t)a->N * a->Cout * esize(a->dtype));
+    w.wt = at; at += align_up((size_t)a->K * a->Cin * a->Cout * esize(a->dtype));
+    w.part = at; at += align_up((size_t)SC_BIAS_BLOCKS * a->Cout * sizeof(float));
     w.bytes = at;
     return w;
 }
@@ -485,38 +467,38 @@ extern "C" {
 
 size_t gdr_subm_table_bytes(int64_t N) {
     if (N < 0 || N > GDR_SUBM_MAX_POINTS) {
-        subm_bad("subm_table_bytes: N must be in 0..GDR_SUBM_MAX_POINTS");
+        invalid_arg("subm_table_bytes: N must be in 0..GDR_SUBM_MAX_POINTS");
         return 0;
     }
     const size_t sort = gdr_serial_sort_bytes(1, N);
     if (!sort) return 0;
-    return 3 * al256((size_t)N * 8) + al256(sort) + 256;      // keys, order, inverse, the sort's own
+    return 3 * align_up((size_t)N * 8) + align_up(sort) + 256;      // keys, order, inverse, the sort's own
 }
 
 int gdr_subm_build_table(const int32_t* indices, int64_t N, const int32_t* spatial_shape, int32_t batch_size, const int32_t* ksize,
                          void* workspace, size_t workspace_bytes, int32_t* nbr, int32_t* rep, int32_t* order, void* stream) {
-    if (N < 0 || N > GDR_SUBM_MAX_POINTS) return subm_bad("subm_build_table: N must be in 0..GDR_SUBM_MAX_POINTS");
-    if (!spatial_shape || !ksize) return subm_bad("subm_build_table: NULL spatial_shape or kernel size");
-    if (batch_size < 1) return subm_bad("subm_build_table: batch_size must be >= 1");
+    if (N < 0 || N > GDR_SUBM_MAX_POINTS) return invalid_arg("subm_build_table: N must be in 0..GDR_SUBM_MAX_POINTS");
+    if (!spatial_shape || !ksize) return invalid_arg("subm_build_table: NULL spatial_shape or kernel size");
+    if (batch_size < 1) return invalid_arg("subm_build_table: batch_size must be >= 1");
     int64_t R = batch_size;
     for (int d = 0; d < 3; ++d) {
-        if (ksize[d] != 1 && ksize[d] != 3 && ksize[d] != 5) return subm_bad("subm_build_table: kernel size must be 1, 3 or 5 per axis");
-        if (spatial_shape[d] < 1) return subm_bad("subm_build_table: spatial_shape must be >= 1 per axis");
-        if (R > (INT64_C(1) << 61) / spatial_shape[d]) return subm_bad("subm_build_table: batch_size * spatial_shape exceeds 2^61 keys");
+        if (ksize[d] != 1 && ksize[d] != 3 && ksize[d] != 5)
+            return invalid_arg("subm_build_table: kernel size must be 1, 3 or 5 per axis");
+        if (spatial_shape[d] < 1) return invalid_arg("subm_build_table: spatial_shape must be >= 1 per axis");
+        if (R > (INT64_C(1) << 61) / spatial_shape[d])
+            return invalid_arg("subm_build_table: batch_size * spatial_shape exceeds 2^61 keys");
         R *= spatial_shape[d];
     }
     if (N == 0) return GDR_OK;
-    if (!indices || !workspace || !nbr || !rep || !order) return subm_bad("subm_build_table: NULL argument");
-    if (((uintptr_t)indices & 15u) || ((uintptr_t)workspace & 255u) || ((uintptr_t)nbr & 3u) || ((uintptr_t)rep & 3u) ||
-        ((uintptr_t)order & 3u))
-        return subm_bad("subm_build_table: unaligned buffer");
+    if (!indices || !workspace || !nbr || !rep || !order) return invalid_arg("subm_build_table: NULL argument");
+    if (misaligned(indices, 15) || misaligned(workspace, 255) || misaligned(nbr, 3) || misaligned(rep, 3) ||
+        misaligned(order, 3))
+        return invalid_arg("subm_build_table: unaligned buffer");
     const size_t need = gdr_subm_table_bytes(N);
-    if (!need || workspace_bytes < need - 256) {
-        set_error("subm_build_table: workspace smaller than gdr_subm_table_bytes", hipSuccess);
-        return GDR_ERR_WORKSPACE;
-    }
+    if (!need || workspace_bytes < need - 256)
+        return workspace_too_small("subm_build_table: workspace smaller than gdr_subm_table_bytes");
     char* base = (char*)workspace;
-    const size_t col = al256((size_t)N * 8);
+    const size_t col = align_up((size_t)N * 8);
     int64_t* key = (int64_t*)base;
     int64_t* ord = (int64_t*)(base + col);
     int64_t* inv = (int64_t*)(base + 2 * col);
@@ -532,62 +514,60 @@ int gdr_subm_build_table(const int32_t* indices, int64_t N, const int32_t* spati
     const hipStream_t st = (hipStream_t)stream;
     const int blocks = div_up(N, SC_BLOCK);
     hipLaunchKernelGGL(subm_key_kernel, dim3(blocks), dim3(SC_BLOCK), 0, st, p);
-    if (const int rc = subm_done("subm_key_kernel")) return rc;
+    if (const int rc = launch_status("subm_key_kernel")) return rc;
     if (const int rc = gdr_serial_sort(key, 1, N, bits, sort_ws, workspace_bytes - 3 * col, ord, inv, stream)) return rc;
     hipLaunchKernelGGL(subm_lookup_kernel, dim3(blocks, p.k0 * p.k1 * p.k2), dim3(SC_BLOCK), 0, st, p);
-    return subm_done("subm_lookup_kernel");
+    return launch_status("subm_lookup_kernel");
 }
 
 int gdr_subm_conv_forward(const gdr_subm_args* a, const void* feat, int64_t feat_stride, const int32_t* nbr, const void* weight,
                           const void* bias, void* out, void* stream) {
-    if (const char* why = subm_check(a)) return subm_bad(why);
+    if (const char* why = subm_check(a)) return invalid_arg(why);
     if (a->N == 0) return GDR_OK;
-    if (!feat || !nbr || !weight || !out) return subm_bad("subm_conv_forward: NULL argument");
-    if (feat_stride < a->Cin) return subm_bad("subm_conv_forward: feature row stride smaller than Cin");
+    if (!feat || !nbr || !weight || !out) return invalid_arg("subm_conv_forward: NULL argument");
+    if (feat_stride < a->Cin) return invalid_arg("subm_conv_forward: feature row stride smaller than Cin");
     const size_t es = esize(a->dtype);
-    if (((uintptr_t)feat & (es - 1)) || ((uintptr_t)bias & (es - 1)) || ((uintptr_t)weight & 15u) || ((uintptr_t)out & 15u) ||
-        ((uintptr_t)nbr & 3u))
-        return subm_bad("subm_conv_forward: unaligned buffer");
+    if (misaligned(feat, es - 1) || misaligned(bias, es - 1) || misaligned(weight, 15) || misaligned(out, 15) ||
+        misaligned(nbr, 3))
+        return invalid_arg("subm_conv_forward: unaligned buffer");
     ConvP p = {};
     p.a = feat; p.w = weight; p.bias = bias; p.nbr = nbr; p.only_rep = nullptr; p.out = out;
     p.a_stride = feat_stride; p.a_plane = 0; p.n = a->N; p.CA = a->Cin; p.CB = a->Cout; p.K = a->K; p.planes = 1;
     p.a_vec = row_vec(feat, feat_stride, a->dtype);
     launch_product(a->dtype, p, (hipStream_t)stream);
-    return subm_done("subm_product_kernel");
+    return launch_status("subm_product_kernel");
 }
 
 size_t gdr_subm_backward_bytes(const gdr_subm_args* a) {
-    if (const char* why = subm_check(a)) { subm_bad(why); return 0; }
+    if (const char* why = subm_check(a)) { invalid_arg(why); return 0; }
     return bwd_workspace(a).bytes + 256;
 }
 
 int gdr_subm_conv_backward(const gdr_subm_args* a, const void* grad_out, const void* feat, int64_t feat_stride, const int32_t* nbr,
                            const int32_t* rep, const int32_t* order, const void* weight, void* workspace, size_t workspace_bytes,
                            void* grad_feat, float* grad_weight, float* grad_bias, void* stream) {
-    if (const char* why = subm_check(a)) return subm_bad(why);
+    if (const char* why = subm_check(a)) return invalid_arg(why);
     if (a->N == 0) return GDR_OK;
     if (!grad_feat && !grad_weight && !grad_bias) return GDR_OK;
     const size_t es = esize(a->dtype);
-    if (!grad_out || ((uintptr_t)grad_out & 15u)) return subm_bad("subm_conv_backward: grad_out NULL or unaligned");
+    if (!grad_out || misaligned(grad_out, 15)) return invalid_arg("subm_conv_backward: grad_out NULL or unaligned");
     const hipStream_t st = (hipStream_t)stream;
     const BwdWs ws = bwd_workspace(a);
     char* base = (char*)workspace;
     const int N = a->N, P = planes_of(a->dtype), dtype = a->dtype;
     if (grad_feat || grad_weight) {
-        if (!nbr || !rep || !order || !workspace) return subm_bad("subm_conv_backward: NULL table or workspace");
-        if (((uintptr_t)workspace & 255u) || ((uintptr_t)nbr & 3u) || ((uintptr_t)rep & 3u) || ((uintptr_t)order & 3u))
-            return subm_bad("subm_conv_backward: unaligned buffer");
-        if (grad_feat && (!weight || ((uintptr_t)weight & 15u) || ((uintptr_t)grad_feat & 15u)))
-            return subm_bad("subm_conv_backward: weight / grad_feat NULL or unaligned");
-        if (grad_weight && (!feat || ((uintptr_t)feat & (es - 1)) || feat_stride < a->Cin || ((uintptr_t)grad_weight & 15u)))
-            return subm_bad("subm_conv_backward: feat / grad_weight NULL, unaligned or row stride smaller than Cin");
-    } else if (!workspace || ((uintptr_t)workspace & 255u)) {
-        return subm_bad("subm_conv_backward: workspace NULL or unaligned");
+        if (!nbr || !rep || !order || !workspace) return invalid_arg("subm_conv_backward: NULL table or workspace");
+        if (misaligned(workspace, 255) || misaligned(nbr, 3) || misaligned(rep, 3) || misaligned(order, 3))
+            return invalid_arg("subm_conv_backward: unaligned buffer");
+        if (grad_feat && (!weight || misaligned(weight, 15) || misaligned(grad_feat, 15)))
+            return invalid_arg("subm_conv_backward: weight / grad_feat NULL or unaligned");
+        if (grad_weight && (!feat || misaligned(feat, es - 1) || feat_stride < a->Cin || misaligned(grad_weight, 15)))
+            return invalid_arg("subm_conv_backward: feat / grad_weight NULL, unaligned or row stride smaller than Cin");
+    } else if (!workspace || misaligned(workspace, 255)) {
+        return invalid_arg("subm_conv_backward: workspace NULL or unaligned");
     }
-    if (workspace_bytes < ws.bytes) {
-        set_error("subm_conv_backward: workspace smaller than gdr_subm_backward_bytes", hipSuccess);
-        return GDR_ERR_WORKSPACE;
-    }
+    if (workspace_bytes < ws.bytes)
+        return workspace_too_small("subm_conv_backward: workspace smaller than gdr_subm_backward_bytes");
     if (grad_bias) {
         int blocks = div_up(N, 64);
         if (blocks > SC_BIAS_BLOCKS) blocks = SC_BIAS_BLOCKS;
@@ -623,7 +603,7 @@ int gdr_subm_conv_backward(const gdr_subm_args* a, const void* grad_out, const v
             GDR_SUBM_DT(subm_gw_kernel, grid, dim3(SC_BLOCK), 0, st, p);
         }
     }
-    return subm_done("subm backward kernels");
+    return launch_status("subm backward kernels");
 }
 
 }  // extern "C"

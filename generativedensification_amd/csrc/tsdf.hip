@@ -47,6 +47,7 @@
 #include <algorithm>
 
 #include "gdr_common.h"
+#include "host_util.h"
 
 namespace gdr {
 
@@ -706,18 +707,6 @@ using namespace gdr;
 
 namespace {
 
-int ts_bad(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_INVALID_ARG;
-}
-
-int ts_hip(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return GDR_OK;
-    set_error(what, e);
-    return GDR_ERR_HIP;
-}
-
 int64_t ts_cells(const gdr_tsdf_args* a) { return (int64_t)a->dims[0] * a->dims[1] * a->dims[2]; }
 
 const char* ts_check(const gdr_tsdf_args* a, bool grid, bool blocks) {
@@ -754,7 +743,7 @@ int scan(uint32_t* data, int64_t n, uint32_t* scratch, hipStream_t st) {
     hipLaunchKernelGGL(scan_reduce_kernel, dim3(tiles), dim3(GDR_BLOCK), 0, st, (const uint32_t*)data, n, scratch);
     hipLaunchKernelGGL(scan_partials_kernel, dim3(1), dim3(GDR_BLOCK), 0, st, scratch, tiles, data + n);
     hipLaunchKernelGGL(scan_apply_kernel, dim3(tiles), dim3(GDR_BLOCK), 0, st, data, n, (const uint32_t*)scratch);
-    return ts_hip("scan");
+    return launch_status("scan");
 }
 
 }  // namespace
@@ -766,8 +755,9 @@ size_t gdr_tsdf_scan_bytes(int64_t n) { return n > 0 ? scan_bytes(n) : 0; }
 int gdr_tsdf_stage(int32_t H, int32_t W, const float* depth, const int64_t* depth_strides, const void* rgb,
                    const int64_t* rgb_strides, int32_t rgb_u8, float depth_trunc, float* depth_out, uint32_t* rgb_out,
                    void* stream) {
-    if (H <= 0 || W <= 0) return ts_bad("tsdf_stage: H, W must be positive");
-    if (!depth || !depth_strides || !rgb || !rgb_strides || !depth_out || !rgb_out) return ts_bad("tsdf_stage: NULL argument");
+    if (H <= 0 || W <= 0) return invalid_arg("tsdf_stage: H, W must be positive");
+    if (!depth || !depth_strides || !rgb || !rgb_strides || !depth_out || !rgb_out)
+        return invalid_arg("tsdf_stage: NULL argument");
     TsStage s;
     s.depth = depth;
     s.ds[0] = depth_strides[0];
@@ -778,62 +768,64 @@ int gdr_tsdf_stage(int32_t H, int32_t W, const float* depth, const int64_t* dept
     s.depth_trunc = depth_trunc;
     hipLaunchKernelGGL(tsdf_stage_kernel, dim3(div_up((int64_t)H * W, GDR_BLOCK)), dim3(GDR_BLOCK), 0, (hipStream_t)stream, s,
                        H, W, depth_out, rgb_out);
-    return ts_hip("tsdf_stage_kernel");
+    return launch_status("tsdf_stage_kernel");
 }
 
 int gdr_tsdf_bounds(const gdr_tsdf_args* a, const gdr_tsdf_view* views, const float* depth, int32_t* bbox, void* stream) {
-    if (const char* why = ts_check(a, false, false)) return ts_bad(why);
-    if (!views || !depth || !bbox) return ts_bad("tsdf_bounds: NULL argument");
+    if (const char* why = ts_check(a, false, false)) return invalid_arg(why);
+    if (!views || !depth || !bbox) return invalid_arg("tsdf_bounds: NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const TsAlloc A = make_alloc(a);
     hipLaunchKernelGGL(tsdf_bounds_init_kernel, dim3(1), dim3(64), 0, st, bbox);
     hipLaunchKernelGGL(tsdf_bounds_kernel, dim3(div_up((int64_t)A.V * A.sh * A.sw, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, A,
                        views, depth, bbox);
-    return ts_hip("tsdf_bounds_kernel");
+    return launch_status("tsdf_bounds_kernel");
 }
 
 int gdr_tsdf_allocate(const gdr_tsdf_args* a, const gdr_tsdf_view* views, const float* depth, uint32_t* cell_mask,
                       int32_t* cell_block, uint32_t* cell_scan, void* scratch, void* stream) {
-    if (const char* why = ts_check(a, true, false)) return ts_bad(why);
-    if (!views || !depth || !cell_mask || !cell_block || !cell_scan || !scratch) return ts_bad("tsdf_allocate: NULL argument");
+    if (const char* why = ts_check(a, true, false)) return invalid_arg(why);
+    if (!views || !depth || !cell_mask || !cell_block || !cell_scan || !scratch)
+        return invalid_arg("tsdf_allocate: NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const TsAlloc A = make_alloc(a);
     const TsGrid G = make_grid(a);
     const int64_t cells = ts_cells(a);
     if (hipMemsetAsync(cell_mask, 0, (size_t)cells * a->words * sizeof(uint32_t), st) != hipSuccess)
-        return ts_hip("tsdf_allocate: clear");
+        return launch_status("tsdf_allocate: clear");
     hipLaunchKernelGGL(tsdf_mark_kernel, dim3(div_up((int64_t)A.V * A.sh * A.sw, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, A, G,
                        a->words, views, depth, cell_mask);
     hipLaunchKernelGGL(tsdf_flag_cells_kernel, dim3(div_up(cells, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, cells, a->words,
                        (const uint32_t*)cell_mask, cell_scan);
-    if (int rc = ts_hip("tsdf_mark_kernel")) return rc;
+    if (int rc = launch_status("tsdf_mark_kernel")) return rc;
     if (int rc = scan(cell_scan, cells, (uint32_t*)scratch, st)) return rc;
     hipLaunchKernelGGL(tsdf_cell_index_kernel, dim3(div_up(cells, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, cells, a->words,
                        (const uint32_t*)cell_mask, (const uint32_t*)cell_scan, cell_block);
-    return ts_hip("tsdf_cell_index_kernel");
+    return launch_status("tsdf_cell_index_kernel");
 }
 
 int gdr_tsdf_integrate(const gdr_tsdf_args* a, const gdr_tsdf_view* views, const float* depth, const uint32_t* rgb,
                        const uint32_t* cell_mask, const int32_t* cell_block, int32_t* blocks, float* vol, void* stream) {
-    if (const char* why = ts_check(a, true, true)) return ts_bad(why);
-    if (!views || !depth || !rgb || !cell_mask || !cell_block || !blocks || !vol) return ts_bad("tsdf_integrate: NULL argument");
+    if (const char* why = ts_check(a, true, true)) return invalid_arg(why);
+    if (!views || !depth || !rgb || !cell_mask || !cell_block || !blocks || !vol)
+        return invalid_arg("tsdf_integrate: NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const TsGrid G = make_grid(a);
     const int64_t cells = ts_cells(a);
     hipLaunchKernelGGL(tsdf_block_list_kernel, dim3(div_up(cells, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, G, cells, cell_block,
                        (int4*)blocks);
-    if (int rc = ts_hip("tsdf_block_list_kernel")) return rc;
+    if (int rc = launch_status("tsdf_block_list_kernel")) return rc;
     const float inv_trunc = 1.f / a->trunc;
     hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(a->n_blocks), dim3(GDR_BLOCK), 0, st, a->H, a->W, a->words, a->voxel,
                        a->trunc, inv_trunc, views, depth, rgb, (const int4*)blocks, cell_mask, make_vol(vol, a->n_blocks));
-    return ts_hip("tsdf_integrate_kernel");
+    return launch_status("tsdf_integrate_kernel");
 }
 
 int gdr_tsdf_mc_count(const gdr_tsdf_args* a, const int32_t* cell_block, const int32_t* blocks, const float* vol,
                       int16_t* cube_case, uint8_t* vflags, uint32_t* vcount, uint32_t* tcount, void* scratch, void* stream) {
-    if (const char* why = ts_check(a, true, true)) return ts_bad(why);
+    if (const char* why = ts_check(a, true, true)) return invalid_arg(why);
     if (!cell_block || !blocks || !vol || !cube_case || !vflags || !vcount || !tcount || !scratch)
-        return ts_bad("tsdf_mc_count: NULL argument");
+        return invalid_arg("tsdf_mc_count: NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const TsGrid G = make_grid(a);
     const TsVol V = make_vol((float*)vol, a->n_blocks);
@@ -842,7 +834,7 @@ int gdr_tsdf_mc_count(const gdr_tsdf_args* a, const int32_t* cell_block, const i
                        V, cube_case, tcount);
     hipLaunchKernelGGL(tsdf_mc_vertex_kernel, dim3(a->n_blocks), dim3(GDR_BLOCK), 0, st, G, cell_block, (const int4*)blocks, V,
                        (const int16_t*)cube_case, vflags, vcount);
-    if (int rc = ts_hip("tsdf_mc_classify_kernel / tsdf_mc_vertex_kernel")) return rc;
+    if (int rc = launch_status("tsdf_mc_classify_kernel / tsdf_mc_vertex_kernel")) return rc;
     if (int rc = scan(vcount, n, (uint32_t*)scratch, st)) return rc;
     return scan(tcount, n, (uint32_t*)scratch, st);
 }
@@ -850,38 +842,40 @@ int gdr_tsdf_mc_count(const gdr_tsdf_args* a, const int32_t* cell_block, const i
 int gdr_tsdf_mc_emit(const gdr_tsdf_args* a, const int32_t* cell_block, const int32_t* blocks, const float* vol,
                      const int16_t* cube_case, const uint8_t* vflags, const uint32_t* voff, const uint32_t* toff,
                      float* vertices, float* colors, int32_t* triangles, void* stream) {
-    if (const char* why = ts_check(a, true, true)) return ts_bad(why);
-    if (!cell_block || !blocks || !vol || !cube_case || !vflags || !voff || !toff) return ts_bad("tsdf_mc_emit: NULL argument");
+    if (const char* why = ts_check(a, true, true)) return invalid_arg(why);
+    if (!cell_block || !blocks || !vol || !cube_case || !vflags || !voff || !toff)
+        return invalid_arg("tsdf_mc_emit: NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const TsGrid G = make_grid(a);
     const TsVol V = make_vol((float*)vol, a->n_blocks);
     if (vertices && colors) {
         hipLaunchKernelGGL(tsdf_mc_emit_vertices_kernel, dim3(a->n_blocks), dim3(GDR_BLOCK), 0, st, G, cell_block,
                            (const int4*)blocks, V, a->voxel, vflags, voff, vertices, colors);
-        if (int rc = ts_hip("tsdf_mc_emit_vertices_kernel")) return rc;
+        if (int rc = launch_status("tsdf_mc_emit_vertices_kernel")) return rc;
     }
     if (triangles) {
         hipLaunchKernelGGL(tsdf_mc_emit_triangles_kernel, dim3(a->n_blocks), dim3(GDR_BLOCK), 0, st, G, cell_block,
                            (const int4*)blocks, cube_case, vflags, voff, toff, triangles);
-        if (int rc = ts_hip("tsdf_mc_emit_triangles_kernel")) return rc;
+        if (int rc = launch_status("tsdf_mc_emit_triangles_kernel")) return rc;
     }
     return GDR_OK;
 }
 
 int gdr_tsdf_clusters(int32_t F, const int64_t* keys, const int64_t* tri_of, int32_t* parent, uint32_t* root_rank,
                       int32_t* label, int32_t* counts, void* scratch, void* stream) {
-    if (F <= 0 || (int64_t)F * 3 > ((int64_t)1 << 31) - 1) return ts_bad("tsdf_clusters: F must be in 1 .. 2^31 / 3");
-    if (!keys || !tri_of || !parent || !root_rank || !label || !counts || !scratch) return ts_bad("tsdf_clusters: NULL argument");
+    if (F <= 0 || (int64_t)F * 3 > ((int64_t)1 << 31) - 1) return invalid_arg("tsdf_clusters: F must be in 1 .. 2^31 / 3");
+    if (!keys || !tri_of || !parent || !root_rank || !label || !counts || !scratch)
+        return invalid_arg("tsdf_clusters: NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = (int64_t)F * 3;
     hipLaunchKernelGGL(tsdf_cc_init_kernel, dim3(div_up(F, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, F, parent, counts);
     hipLaunchKernelGGL(tsdf_cc_hook_kernel, dim3(div_up(n - 1, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, n, keys, tri_of, parent);
     hipLaunchKernelGGL(tsdf_cc_compress_kernel, dim3(div_up(F, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, F, parent, root_rank);
-    if (int rc = ts_hip("tsdf_cc_hook_kernel")) return rc;
+    if (int rc = launch_status("tsdf_cc_hook_kernel")) return rc;
     if (int rc = scan(root_rank, F, (uint32_t*)scratch, st)) return rc;
     hipLaunchKernelGGL(tsdf_cc_label_kernel, dim3(div_up(F, GDR_BLOCK)), dim3(GDR_BLOCK), 0, st, F, (const int*)parent,
                        (const uint32_t*)root_rank, label, counts);
-    return ts_hip("tsdf_cc_label_kernel");
+    return launch_status("tsdf_cc_label_kernel");
 }
 
 }  // extern "C"

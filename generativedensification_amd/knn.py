@@ -5,11 +5,10 @@ waits for the device: the cells per axis are chosen by a kernel and stay on the 
 searchsorted over a table whose size depends on N alone."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib as L
+from . import _marshal as M
 
 # the box spans the (N >> TRIM_SHIFT)-th smallest to the (N >> TRIM_SHIFT)-th largest coordinate of every axis: up to
 # 0.4 % of the points per side fall outside it and are binned into the edge cells (csrc/knn.hip: still exact)
@@ -24,7 +23,7 @@ def grid(pts: torch.Tensor, cells_per_axis: int | None = None):
     g = int(cells_per_axis) if cells_per_axis else 0
     if g < 0 or g > 1024:
         raise ValueError("cells_per_axis must be in 1..1024")
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = M.stream()
     srt = pts.t().contiguous().sort(dim=1).values
     k = N >> TRIM_SHIFT
     bbox = torch.cat([srt[:, k], srt[:, N - 1 - k]]).contiguous()
@@ -50,7 +49,7 @@ def dist2(points: torch.Tensor, cells_per_axis: int | None = None, return_work: 
     if N == 0:
         return (out, work) if return_work else out
     with torch.no_grad(), torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = M.stream()
         bbox, gdim, max_cells = grid(pts, cells_per_axis)
         cell = torch.empty(N, dtype=torch.int32, device=dev)
         L.check(lib.gsr_knn_cells_axes(pts.data_ptr(), N, bbox.data_ptr(), gdim.data_ptr(), cell.data_ptr(), stream),

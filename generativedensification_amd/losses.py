@@ -4,11 +4,10 @@ forward and one elementwise kernel backward instead of ~12 torch launches per vi
 gradients as `synthetic.view_loss` on the dict `Renderer.render_img` returns."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib as L
+from . import _marshal as M
 
 
 class _ViewLoss(torch.autograd.Function):
@@ -20,7 +19,7 @@ class _ViewLoss(torch.autograd.Function):
         H, W = int(color.shape[-2]), int(color.shape[-1])
         loss = torch.zeros((), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            st = M.stream()
             L.check(lib.gdr_view_loss_forward(color.data_ptr(), depth.data_ptr(), alpha.data_ptr(), target_chw.data_ptr(),
                                               H, W, float(w_depth), float(w_alpha), loss.data_ptr(), st),
                     "gdr_view_loss_forward")
@@ -39,7 +38,7 @@ class _ViewLoss(torch.autograd.Function):
         dd = torch.empty(1, H, W, dtype=torch.float32, device=dev)
         da = torch.empty(1, H, W, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            st = M.stream()
             L.check(lib.gdr_view_loss_backward(color.data_ptr(), target.data_ptr(), H, W, w_depth, w_alpha, g.data_ptr(),
                                                dc.data_ptr(), dd.data_ptr(), da.data_ptr(), st), "gdr_view_loss_backward")
         return dc, dd, da, None, None, None
@@ -65,7 +64,7 @@ class _SurfelViewLoss(torch.autograd.Function):
         w = (float(depth_ratio), float(w_dist), float(w_normal), float(w_depth), float(w_alpha))
         loss = torch.zeros((), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            st = M.stream()
             L.check(lib.gsr_view_loss_forward(color.data_ptr(), allmap.data_ptr(), rays.data_ptr(), view.data_ptr(),
                                               target_chw.data_ptr(), H, W, *w, loss.data_ptr(), st), "gsr_view_loss_forward")
         ctx.save_for_backward(color, allmap, rays, view, target_chw)
@@ -82,7 +81,7 @@ class _SurfelViewLoss(torch.autograd.Function):
         dc, da = torch.empty_like(color), torch.empty_like(allmap)
         scratch = torch.empty(9, H, W, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            st = M.stream()
             L.check(lib.gsr_view_loss_backward(color.data_ptr(), allmap.data_ptr(), rays.data_ptr(), view.data_ptr(),
                                                target.data_ptr(), H, W, *ctx.w, g.data_ptr(), scratch.data_ptr(),
                                                dc.data_ptr(), da.data_ptr(), st), "gsr_view_loss_backward")

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _marshal as M
 from .camera import mesh_path_cameras
 
 __all__ = ["TriangleMesh", "TSDFVolume", "mesh_path_cameras", "crop_to_aabb", "cluster_connected_triangles", "keep_cluster_mask",
@@ -39,14 +40,6 @@ def _empty_mesh(device) -> TriangleMesh:
     return TriangleMesh(torch.zeros(0, 3, dtype=torch.float32, device=device),
                         torch.zeros(0, 3, dtype=torch.int32, device=device),
                         torch.zeros(0, 3, dtype=torch.float32, device=device))
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class TSDFVolume:
@@ -101,9 +94,9 @@ class TSDFVolume:
         c_out = torch.empty(H, W, dtype=torch.int32, device=depth.device)
         lib = L.load()
         with torch.cuda.device(depth.device):
-            L.check(lib.gdr_tsdf_stage(H, W, _ptr(depth), (C.c_int64 * 2)(*depth.stride()), _ptr(rgb),
-                                       (C.c_int64 * 3)(*rgb.stride()), int(rgb.dtype == torch.uint8), float(depth_trunc),
-                                       _ptr(d_out), _ptr(c_out), _stream()), "gdr_tsdf_stage")
+            L.check(lib.gdr_tsdf_stage(H, W, M.ptr(depth), M.strides(depth), M.ptr(rgb),
+                                       M.strides(rgb), int(rgb.dtype == torch.uint8), float(depth_trunc),
+                                       M.ptr(d_out), M.ptr(c_out), M.stream()), "gdr_tsdf_stage")
         self._depth.append(d_out)
         self._rgb.append(c_out)
         self._views.append(rec)
@@ -125,11 +118,11 @@ class TSDFVolume:
         lib, dev = L.load(), self._depth[0].device
         a = self._args()
         with torch.cuda.device(dev):
-            st = _stream()
+            st = M.stream()
             depth, rgb = torch.stack(self._depth), torch.stack(self._rgb)
             views = torch.from_numpy(np.stack(self._views)).to(dev)
             bbox = torch.empty(6, dtype=torch.int32, device=dev)
-            L.check(lib.gdr_tsdf_bounds(C.byref(a), _ptr(views), _ptr(depth), _ptr(bbox), st), "gdr_tsdf_bounds")
+            L.check(lib.gdr_tsdf_bounds(C.byref(a), M.ptr(views), M.ptr(depth), M.ptr(bbox), st), "gdr_tsdf_bounds")
             bb = bbox.cpu().tolist()
             if bb[0] > bb[3]:   # no depth at all
                 self._set_empty(dev, a.words)
@@ -146,8 +139,8 @@ class TSDFVolume:
             cell_block = torch.empty(cells, dtype=torch.int32, device=dev)
             cell_scan = torch.empty(cells + 1, dtype=torch.int32, device=dev)
             scratch = torch.empty(int(lib.gdr_tsdf_scan_bytes(cells)), dtype=torch.uint8, device=dev)
-            L.check(lib.gdr_tsdf_allocate(C.byref(a), _ptr(views), _ptr(depth), _ptr(cell_mask), _ptr(cell_block),
-                                          _ptr(cell_scan), _ptr(scratch), st), "gdr_tsdf_allocate")
+            L.check(lib.gdr_tsdf_allocate(C.byref(a), M.ptr(views), M.ptr(depth), M.ptr(cell_mask), M.ptr(cell_block),
+                                          M.ptr(cell_scan), M.ptr(scratch), st), "gdr_tsdf_allocate")
             nb = int(cell_scan[cells].item())
             if nb > self.max_blocks:
                 raise RuntimeError(f"TSDFVolume: {nb} blocks touched > max_blocks={self.max_blocks} "
@@ -156,8 +149,8 @@ class TSDFVolume:
             a.n_blocks = nb
             blocks = torch.empty(nb, 4, dtype=torch.int32, device=dev)
             vol = torch.empty(5, nb, L.GDR_TSDF_R ** 3, dtype=torch.float32, device=dev)
-            L.check(lib.gdr_tsdf_integrate(C.byref(a), _ptr(views), _ptr(depth), _ptr(rgb), _ptr(cell_mask),
-                                           _ptr(cell_block), _ptr(blocks), _ptr(vol), st), "gdr_tsdf_integrate")
+            L.check(lib.gdr_tsdf_integrate(C.byref(a), M.ptr(views), M.ptr(depth), M.ptr(rgb), M.ptr(cell_mask),
+                                           M.ptr(cell_block), M.ptr(blocks), M.ptr(vol), st), "gdr_tsdf_integrate")
         self._a, self._cell_mask, self._cell_block, self._blocks4, self._vol = a, cell_mask, cell_block, blocks, vol
         self.blocks = blocks[:, :3]
         self.block_views = cell_mask.view(cells, a.words)[blocks[:, 3].long()]
@@ -181,21 +174,21 @@ class TSDFVolume:
         lib = L.load()
         n = a.n_blocks * L.GDR_TSDF_R ** 3
         with torch.cuda.device(dev):
-            st = _stream()
+            st = M.stream()
             cube_case = torch.empty(n, dtype=torch.int16, device=dev)
             vflags = torch.empty(n, dtype=torch.uint8, device=dev)
             vcount = torch.empty(n + 1, dtype=torch.int32, device=dev)
             tcount = torch.empty(n + 1, dtype=torch.int32, device=dev)
             scratch = torch.empty(int(lib.gdr_tsdf_scan_bytes(n)), dtype=torch.uint8, device=dev)
-            args = (C.byref(a), _ptr(self._cell_block), _ptr(self._blocks4), _ptr(self._vol))
-            L.check(lib.gdr_tsdf_mc_count(*args, _ptr(cube_case), _ptr(vflags), _ptr(vcount), _ptr(tcount), _ptr(scratch), st),
-                    "gdr_tsdf_mc_count")
+            args = (C.byref(a), M.ptr(self._cell_block), M.ptr(self._blocks4), M.ptr(self._vol))
+            L.check(lib.gdr_tsdf_mc_count(*args, M.ptr(cube_case), M.ptr(vflags), M.ptr(vcount), M.ptr(tcount),
+                                          M.ptr(scratch), st), "gdr_tsdf_mc_count")
             nv, nf = torch.stack([vcount[n], tcount[n]]).cpu().tolist()
             verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
             cols = torch.empty(nv, 3, dtype=torch.float32, device=dev)
             tris = torch.empty(nf, 3, dtype=torch.int32, device=dev)
-            L.check(lib.gdr_tsdf_mc_emit(*args, _ptr(cube_case), _ptr(vflags), _ptr(vcount), _ptr(tcount),
-                                         _ptr(verts) if nv else None, _ptr(cols) if nv else None, _ptr(tris) if nf else None,
+            L.check(lib.gdr_tsdf_mc_emit(*args, M.ptr(cube_case), M.ptr(vflags), M.ptr(vcount), M.ptr(tcount),
+                                         M.ptr(verts) if nv else None, M.ptr(cols) if nv else None, M.ptr(tris) if nf else None,
                                          st), "gdr_tsdf_mc_emit")
         return TriangleMesh(verts, tris, cols)
 
@@ -238,8 +231,8 @@ def cluster_connected_triangles(mesh: TriangleMesh):
         label = torch.empty(F, dtype=torch.int32, device=dev)
         counts = torch.empty(F, dtype=torch.int32, device=dev)
         scratch = torch.empty(int(lib.gdr_tsdf_scan_bytes(F)), dtype=torch.uint8, device=dev)
-        L.check(lib.gdr_tsdf_clusters(F, _ptr(keys), _ptr(tri_of), _ptr(parent), _ptr(rank), _ptr(label), _ptr(counts),
-                                      _ptr(scratch), _stream()), "gdr_tsdf_clusters")
+        L.check(lib.gdr_tsdf_clusters(F, M.ptr(keys), M.ptr(tri_of), M.ptr(parent), M.ptr(rank), M.ptr(label), M.ptr(counts),
+                                      M.ptr(scratch), M.stream()), "gdr_tsdf_clusters")
         K = int(rank[F].item())
     return label, counts[:K]
 

@@ -21,23 +21,11 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import _marshal as M
 
 __all__ = ["point_feats", "sample_views", "MAX_VIEWS", "MAX_CHANNELS", "MAX_SIDE"]
 
 MAX_VIEWS, MAX_CHANNELS, MAX_SIDE = L.GDR_PF_MAX_VIEWS, L.GDR_PF_MAX_CHANNELS, L.GDR_PF_MAX_SIDE
-
-
-def _strides(t: torch.Tensor, dims=None):
-    s = t.stride() if dims is None else t.stride()[:dims]
-    return (C.c_int64 * len(s))(*s)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _args(N, V, Cn, H, W):
@@ -57,9 +45,9 @@ class _PointFeats(torch.autograd.Function):
         with torch.cuda.device(dev):
             out = torch.empty(N, V, 8, dtype=torch.float32, device=dev)
             L.check(L.load().gdr_point_feats_forward(
-                C.byref(_args(N, V, 0, H, W)), img_ref.data_ptr(), _strides(img_ref), image.data_ptr(), _strides(image),
-                acc_map.data_ptr(), _strides(acc_map), depth.data_ptr(), _strides(depth, 3), points.data_ptr(), _strides(points),
-                w2cs.data_ptr(), ixts.data_ptr(), out.data_ptr(), _stream()), "gdr_point_feats_forward")
+                C.byref(_args(N, V, 0, H, W)), img_ref.data_ptr(), M.strides(img_ref), image.data_ptr(), M.strides(image),
+                acc_map.data_ptr(), M.strides(acc_map), depth.data_ptr(), M.strides(depth, 3), points.data_ptr(), M.strides(points),
+                w2cs.data_ptr(), ixts.data_ptr(), out.data_ptr(), M.stream()), "gdr_point_feats_forward")
         ctx.save_for_backward(img_ref, image, acc_map, depth, points, w2cs, ixts)
         return out
 
@@ -80,9 +68,9 @@ class _PointFeats(torch.autograd.Function):
                      for s, w in zip((img_ref, image, acc_map, depth), need[:4])]
             grads.append(torch.empty(N, 3, dtype=torch.float32, device=dev) if need[4] else None)
             L.check(L.load().gdr_point_feats_backward(
-                C.byref(_args(N, V, 0, H, W)), gout.data_ptr(), img_ref.data_ptr(), _strides(img_ref), image.data_ptr(),
-                _strides(image), acc_map.data_ptr(), _strides(acc_map), depth.data_ptr(), _strides(depth, 3), points.data_ptr(),
-                _strides(points), w2cs.data_ptr(), ixts.data_ptr(), *(_ptr(g) for g in grads), _stream()),
+                C.byref(_args(N, V, 0, H, W)), gout.data_ptr(), img_ref.data_ptr(), M.strides(img_ref), image.data_ptr(),
+                M.strides(image), acc_map.data_ptr(), M.strides(acc_map), depth.data_ptr(), M.strides(depth, 3), points.data_ptr(),
+                M.strides(points), w2cs.data_ptr(), ixts.data_ptr(), *(M.ptr(g) for g in grads), M.stream()),
                 "gdr_point_feats_backward")
         return (*grads, None, None)
 
@@ -99,8 +87,8 @@ class _SampleViews(torch.autograd.Function):
             out = torch.empty(V, Cn, N, dtype=torch.float32, device=dev)
             z = torch.empty(V, N, dtype=torch.float32, device=dev)
             L.check(L.load().gdr_sample_views_forward(
-                C.byref(_args(N, V, Cn, H, W)), images.data_ptr(), _strides(images), points.data_ptr(), _strides(points),
-                w2cs.data_ptr(), ixts.data_ptr(), out.data_ptr(), z.data_ptr(), _stream()), "gdr_sample_views_forward")
+                C.byref(_args(N, V, Cn, H, W)), images.data_ptr(), M.strides(images), points.data_ptr(), M.strides(points),
+                w2cs.data_ptr(), ixts.data_ptr(), out.data_ptr(), z.data_ptr(), M.stream()), "gdr_sample_views_forward")
         ctx.save_for_backward(images, points, w2cs, ixts)
         return out, z
 
@@ -120,8 +108,8 @@ class _SampleViews(torch.autograd.Function):
             g_img = torch.zeros(images.shape, dtype=torch.float32, device=dev) if need_img else None
             g_pts = torch.empty(N, 3, dtype=torch.float32, device=dev) if need_pts else None
             L.check(L.load().gdr_sample_views_backward(
-                C.byref(_args(N, V, Cn, H, W)), gout.data_ptr(), _ptr(gz), images.data_ptr(), _strides(images), points.data_ptr(),
-                _strides(points), w2cs.data_ptr(), ixts.data_ptr(), _ptr(g_img), _ptr(g_pts), _stream()),
+                C.byref(_args(N, V, Cn, H, W)), gout.data_ptr(), M.ptr(gz), images.data_ptr(), M.strides(images), points.data_ptr(),
+                M.strides(points), w2cs.data_ptr(), ixts.data_ptr(), M.ptr(g_img), M.ptr(g_pts), M.stream()),
                 "gdr_sample_views_backward")
         return g_img, g_pts, None, None
 

@@ -20,13 +20,14 @@ import ctypes as C
 import math
 import os as _os
 import threading
-from typing import NamedTuple, Optional
+from typing import NamedTuple
 
 import torch
 from torch import nn
 
 from . import _debug as K
 from . import _lib as L
+from . import _marshal as M
 from . import viewgroup      # at module import (its torch probe must not wait for a first call under no_grad / in a backward)
 
 
@@ -45,8 +46,7 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+_ptr = M.ptr_or_none_if_empty
 
 
 _EMPTY: dict = {}
@@ -195,11 +195,8 @@ def _view_streams(dev, n):
         return pool[:n]
 
 
-_raw_stream = torch._C._cuda_getCurrentRawStream   # (torch.cuda.current_stream() builds a Stream object: 9 us per call)
-
-
-def _stream():
-    return C.c_void_p(_raw_stream(torch.cuda.current_device()))
+_raw_stream = M.raw_stream
+_stream = M.stream
 
 
 class _SideViews:

@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import _marshal as M
 from .rasterizer import GaussianRasterizationSettings
 from .surfel_rasterizer import (GaussianRasterizer, _RasterizeSurfels, render_surfel_views_loss_raw,
                                 render_surfel_views_raw)
@@ -63,8 +64,6 @@ class _SurfelMaps(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, allmap, rays, viewmatrix, depth_ratio):
-        import ctypes as C
-
         lib = L.load()
         dev = allmap.device
         allmap = allmap.contiguous()
@@ -77,27 +76,24 @@ class _SurfelMaps(torch.autograd.Function):
         with torch.cuda.device(dev):
             L.check(lib.gsr_maps_forward(allmap.data_ptr(), rays.data_ptr(), view.data_ptr(), H, W, float(depth_ratio),
                                          depth.data_ptr(), acc.data_ptr(), rn.data_ptr(), dn.data_ptr(), dist.data_ptr(),
-                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "gsr_maps_forward")
+                                         M.stream()), "gsr_maps_forward")
         ctx.save_for_backward(allmap, rays, view)
         ctx.depth_ratio = float(depth_ratio)
         return depth, acc, rn, dn, dist
 
     @staticmethod
     def backward(ctx, g_depth, g_acc, g_rn, g_dn, g_dist):
-        import ctypes as C
-
         lib = L.load()
         allmap, rays, view = ctx.saved_tensors
         dev = allmap.device
         H, W = int(allmap.shape[1]), int(allmap.shape[2])
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_depth, g_acc, g_rn, g_dn, g_dist)]
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         out = torch.empty_like(allmap)
         scratch = torch.empty(6, H, W, dtype=torch.float32, device=dev) if gs[3] is not None else None
         with torch.cuda.device(dev):
             L.check(lib.gsr_maps_backward(allmap.data_ptr(), rays.data_ptr(), view.data_ptr(), H, W, ctx.depth_ratio,
-                                          ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gs[4]), ptr(scratch),
-                                          out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                          M.ptr(gs[0]), M.ptr(gs[1]), M.ptr(gs[2]), M.ptr(gs[3]), M.ptr(gs[4]), M.ptr(scratch),
+                                          out.data_ptr(), M.stream()),
                     "gsr_maps_backward")
         return out, None, None, None
 

@@ -19,15 +19,12 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import _marshal as M
 
 __all__ = ["encode", "decode", "serialize", "serialization", "patch_tables", "ORDERS", "SORT_TILE"]
 
 ORDERS = tuple(L.GDR_SERIAL_ORDERS)
 SORT_TILE = L.GDR_SERIAL_SORT_TILE     # keys per workgroup of the sort
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _order_ids(orders):
@@ -79,9 +76,9 @@ def _encode(grid_coord, batch, depth, names, ids):
     N, k, dev = grid_coord.shape[0], len(names), grid_coord.device
     with torch.cuda.device(dev):
         code = torch.empty(k, N, dtype=torch.int64, device=dev)
-        L.check(L.load().gdr_serial_encode(grid_coord.data_ptr(), (C.c_int64 * 2)(*grid_coord.stride()),
+        L.check(L.load().gdr_serial_encode(grid_coord.data_ptr(), M.strides(grid_coord),
                                            int(grid_coord.dtype == torch.int64), None if batch is None else batch.data_ptr(),
-                                           N, depth, k, ids, code.data_ptr(), _stream()), "gdr_serial_encode")
+                                           N, depth, k, ids, code.data_ptr(), M.stream()), "gdr_serial_encode")
     return code
 
 
@@ -113,7 +110,7 @@ def decode(code, depth=16, order="z"):
         grid = torch.empty(N, 3, dtype=torch.int64, device=dev)
         batch = torch.empty(N, dtype=torch.int64, device=dev)
         L.check(L.load().gdr_serial_decode(code.data_ptr(), N, depth, L.GDR_SERIAL_ORDERS[order], grid.data_ptr(),
-                                           batch.data_ptr(), _stream()), "gdr_serial_decode")
+                                           batch.data_ptr(), M.stream()), "gdr_serial_decode")
     return grid, batch
 
 
@@ -143,10 +140,9 @@ def serialize(grid_coord, batch, depth, orders, num_segments=None):
         nbytes = lib.gdr_serial_sort_bytes(k, N)
         if nbytes == 0:
             L.check(-1, "gdr_serial_sort_bytes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        base = (ws.data_ptr() + 255) & ~255
-        L.check(lib.gdr_serial_sort(code.data_ptr(), k, N, bits, base, nbytes - (base - ws.data_ptr()), order.data_ptr(),
-                                    inverse.data_ptr(), _stream()), "gdr_serial_sort")
+        ws, base, usable = M.workspace(nbytes, dev)
+        L.check(lib.gdr_serial_sort(code.data_ptr(), k, N, bits, base, usable, order.data_ptr(), inverse.data_ptr(), M.stream()),
+                "gdr_serial_sort")
     return code, order, inverse
 
 
@@ -228,5 +224,5 @@ def patch_tables(offset, patch_size, device=None):
         unpad = torch.empty(prev, dtype=torch.int64, device=dev)
         cu = torch.empty(n_seq + 1, dtype=torch.int32, device=dev)
         L.check(L.load().gdr_serial_patch_tables(off_dev.data_ptr(), B, P, prev, total, n_seq, pad.data_ptr(), unpad.data_ptr(),
-                                                 cu.data_ptr(), _stream()), "gdr_serial_patch_tables")
+                                                 cu.data_ptr(), M.stream()), "gdr_serial_patch_tables")
     return pad, unpad, cu

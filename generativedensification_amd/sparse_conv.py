@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import _marshal as M
 
 __all__ = ["SparseConvTensor", "SubMConv3d", "SparseModule", "SubMTable", "build_table", "subm_conv3d", "is_spconv_module",
            "AUTOCAST_DTYPE", "TABLES_BUILT"]
@@ -32,10 +33,6 @@ AUTOCAST_DTYPE = torch.float16     # what the layer computes in under autocast (
 TABLES_BUILT = 0                   # neighbour tables built by this process (tests: two layers of one indice_key build one)
 _DTYPES = {torch.float16: L.GDR_SUBM_DTYPES["f16"], torch.bfloat16: L.GDR_SUBM_DTYPES["bf16"],
            torch.float32: L.GDR_SUBM_DTYPES["f32"]}
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _triple(v, what):
@@ -81,11 +78,10 @@ def build_table(indices, spatial_shape, batch_size, kernel_size) -> SubMTable:
         nbytes = lib.gdr_subm_table_bytes(N)
         if nbytes == 0:
             L.check(-1, "gdr_subm_table_bytes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        base = (ws.data_ptr() + 255) & ~255
+        ws, base, usable = M.workspace(nbytes, dev)
         L.check(lib.gdr_subm_build_table(indices.data_ptr(), N, (C.c_int32 * 3)(*shape), int(batch_size), (C.c_int32 * 3)(*ksize),
-                                         base, nbytes - (base - ws.data_ptr()), nbr.data_ptr(), rep.data_ptr(), order.data_ptr(),
-                                         _stream()), "gdr_subm_build_table")
+                                         base, usable, nbr.data_ptr(), rep.data_ptr(), order.data_ptr(), M.stream()),
+                "gdr_subm_build_table")
     TABLES_BUILT += 1
     return SubMTable(nbr, rep, order, ksize)
 
@@ -115,7 +111,7 @@ class _SubMConvFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             out = torch.empty(N, Cout, dtype=dtype, device=dev)
             L.check(lib.gdr_subm_conv_forward(C.byref(a), f.data_ptr(), f.stride(0) if N else Cin, table.nbr.data_ptr(),
-                                              w.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(), _stream()),
+                                              w.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(), M.stream()),
                     "gdr_subm_conv_forward")
         if any(ctx.needs_input_grad[:3]):      # (nothing is kept under no_grad)
             ctx.save_for_backward(f if ctx.needs_input_grad[1] else None, w if ctx.needs_input_grad[0] else None)
@@ -147,13 +143,12 @@ class _SubMConvFunction(torch.autograd.Function):
                 nbytes = lib.gdr_subm_backward_bytes(C.byref(a))
                 if nbytes == 0:
                     L.check(-1, "gdr_subm_backward_bytes")
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                base = (ws.data_ptr() + 255) & ~255
+                ws, base, usable = M.workspace(nbytes, dev)
                 L.check(lib.gdr_subm_conv_backward(
                     C.byref(a), grad_out.data_ptr(), None if f is None else f.data_ptr(), 0 if f is None else f.stride(0),
                     table.nbr.data_ptr(), table.rep.data_ptr(), table.order.data_ptr(), None if w is None else w.data_ptr(), base,
-                    nbytes - (base - ws.data_ptr()), None if gf is None else gf.data_ptr(), None if gw is None else gw.data_ptr(),
-                    None if gb is None else gb.data_ptr(), _stream()), "gdr_subm_conv_backward")
+                    usable, None if gf is None else gf.data_ptr(), None if gw is None else gw.data_ptr(),
+                    None if gb is None else gb.data_ptr(), M.stream()), "gdr_subm_conv_backward")
         if gw is not None:
             gw = gw.view(a.Cout, *table.ksize, a.Cin).to(ctx.w_dtype)
         if gb is not None:

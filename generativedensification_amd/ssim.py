@@ -17,6 +17,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import _marshal as M
 
 __all__ = ["ssim", "ms_ssim", "SSIM", "MS_SSIM"]
 
@@ -30,10 +31,6 @@ def _fspecial_gauss_1d(size: int, sigma: float) -> torch.Tensor:
     return (g / g.sum()).reshape(1, 1, -1)
 
 
-def _strides(t: torch.Tensor):
-    return (C.c_int64 * 4)(*t.stride())
-
-
 class _SSIMFunction(torch.autograd.Function):
     """(X, Y) fp32 (B, C, H, W) on the GPU -> (B, C) per-plane value (ssim, relu(ssim) or the MS-SSIM product)."""
 
@@ -44,8 +41,8 @@ class _SSIMFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             ws = torch.empty(int(lib.gdr_ssim_workspace_bytes(C.byref(args))), dtype=torch.uint8, device=dev)
             out = torch.empty(args.B, args.C, dtype=torch.float32, device=dev)
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            L.check(lib.gdr_ssim_forward(C.byref(args), X.data_ptr(), _strides(X), Y.data_ptr(), _strides(Y), ws.data_ptr(),
+            st = M.stream()
+            L.check(lib.gdr_ssim_forward(C.byref(args), X.data_ptr(), M.strides(X), Y.data_ptr(), M.strides(Y), ws.data_ptr(),
                                          out.data_ptr(), st), "gdr_ssim_forward")
         ctx.save_for_backward(X, Y)
         ctx.ws, ctx.args = ws, args
@@ -63,10 +60,10 @@ class _SSIMFunction(torch.autograd.Function):
         dY = torch.empty_like(Y) if want_dy else None
         with torch.cuda.device(dev):
             scratch = torch.empty(int(lib.gdr_ssim_scratch_bytes(C.byref(args), int(want_dy))), dtype=torch.uint8, device=dev)
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            L.check(lib.gdr_ssim_backward(C.byref(args), X.data_ptr(), _strides(X), Y.data_ptr(), _strides(Y), ctx.ws.data_ptr(),
-                                          g.data_ptr(), dX.data_ptr(), _strides(dX), dY.data_ptr() if want_dy else None,
-                                          _strides(dY) if want_dy else None, scratch.data_ptr(), st), "gdr_ssim_backward")
+            st = M.stream()
+            L.check(lib.gdr_ssim_backward(C.byref(args), X.data_ptr(), M.strides(X), Y.data_ptr(), M.strides(Y), ctx.ws.data_ptr(),
+                                          g.data_ptr(), dX.data_ptr(), M.strides(dX), dY.data_ptr() if want_dy else None,
+                                          M.strides(dY) if want_dy else None, scratch.data_ptr(), st), "gdr_ssim_backward")
         return dX, dY, None
 
 
