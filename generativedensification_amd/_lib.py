@@ -175,6 +175,11 @@ GDR_SUBM_DTYPES = {"f16": 0, "bf16": 1, "f32": 2}
 GDR_SUBM_MAX_TAPS, GDR_SUBM_MAX_CHANNELS, GDR_SUBM_MAX_POINTS = 125, 512, 1 << 30
 
 
+GDR_SEG_ROWS, GDR_SEG_MAX_CHANNELS = 32, 65536
+GDR_SEG_DTYPES = {"f16": 0, "bf16": 1, "f32": 2, "i64": 3}
+GDR_SEG_OPS = {"sum": 0, "mean": 1, "min": 2, "max": 3}
+
+
 class GdrSubmArgs(C.Structure):   # include/gdr.h gdr_subm_args
     _fields_ = [("N", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("K", C.c_int32), ("dtype", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -321,6 +326,13 @@ _PROTOS = {
     "gdr_subm_backward_bytes": (C.c_size_t, [C.POINTER(GdrSubmArgs)]),
     "gdr_subm_conv_backward": (C.c_int, [C.POINTER(GdrSubmArgs), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5
                                + [C.c_size_t] + [C.c_void_p] * 4),
+    "gdr_seg_reduce_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "gdr_seg_reduce": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_seg_gather": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdr_seg_route": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdr_seg_ptr_from_sorted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),
