@@ -149,6 +149,36 @@ __device__ __forceinline__ void stage_rows_in(const float* __restrict__ g, int r
     }
 }
 
+// The same copy in two steps, for a caller that has loads of its own to issue while the rows are on their way.  As one
+// step (stage_rows_in) every float4 is loaded, waited for and written inside a branch of its own before the next one is
+// loaded: ROWF / 4 memory latencies in a row (12 at degree 3) at the head of every workgroup.  Here nothing is branched
+// on: a thread whose float4 lies past the end of the span copies the span's last float4 again (same value to the same
+// LDS address as its owner), so stage_rows_load is ROWF / 4 loads back to back and stage_rows_store waits for each only
+// where it is written.  Those duplicate LDS writes are deliberate: several lanes store one value to one address, which
+// the hardware serialises, and only the last workgroup of a launch has such lanes (up to ROWF / 4 redundant writes per
+// lane there).  The multi-view K9 uses this pair; the multi-view K1 at degree 1, the single-view K9 and
+// preprocess_surfel.hip still call stage_rows_in and should gain the same way (not done here: not measured).
+template <int ROWF>
+__device__ __forceinline__ void stage_rows_load(const float* __restrict__ g, int row0, int nrows,
+                                                float4 (&t)[RowStage<ROWF>::Q]) {
+    constexpr int Q = RowStage<ROWF>::Q;
+    const float4* src = reinterpret_cast<const float4*>(g + (size_t)row0 * ROWF);
+    const int last = nrows * Q - 1;
+#pragma unroll
+    for (int j = 0; j < Q; ++j) t[j] = src[min((int)threadIdx.x + GDR_BLOCK * j, last)];
+}
+template <int ROWF>
+__device__ __forceinline__ void stage_rows_store(const float4 (&t)[RowStage<ROWF>::Q], int nrows, float* lds) {
+    constexpr int Q = RowStage<ROWF>::Q, STRIDE = RowStage<ROWF>::STRIDE;
+    const int last = nrows * Q - 1;
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+        const int idx = min((int)threadIdx.x + GDR_BLOCK * j, last);
+        const int row = idx / Q, c = idx - row * Q;
+        *reinterpret_cast<float4*>(lds + row * STRIDE + 4 * c) = t[j];
+    }
+}
+
 // LDS -> global rows (optionally added to what is there), same mapping
 template <int ROWF>
 __device__ __forceinline__ void stage_rows_out(float* __restrict__ g, int row0, int nrows, const float* lds,

@@ -788,12 +788,31 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_views_kernel(
     const int row0 = blockIdx.x * GDR_BLOCK;
     const int nrows = min(GDR_BLOCK, N - row0);
     const int i = row0 + threadIdx.x;
-    if (STAGED) {
-        stage_rows_in<STAGED ? ROWF : 4>(shs, row0, nrows, lds_rows);
-        __syncthreads();
-    }
     const bool in_range = i < N;
     if (!STAGED && !in_range) return;
+    // The loads that depend on no other are written in front of the first wait: the workgroup's SH rows (STAGED), this
+    // Gaussian's mean and covariance and, with PREFETCH, its radius in every view.  In the gfx950 code the rows and the
+    // radii are in flight together in front of the barrier (one memory latency instead of ROWF / 4 + 1); the compiler
+    // sinks the mean / covariance loads behind the barrier into the in_range block, where they share a second latency with
+    // the first view's record.  A lane past the end reads Gaussian N - 1 and uses nothing of it.
+    const int il = min(i, N - 1);
+    float4 rows_in[RowStage<STAGED ? ROWF : 4>::Q];
+    if (STAGED) stage_rows_load<STAGED ? ROWF : 4>(shs, row0, nrows, rows_in);
+    const float px_ = means3D[3 * il], py_ = means3D[3 * il + 1], pz_ = means3D[3 * il + 2];
+    float c6[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c6[k] = cov3D[6 * il + k];
+    // the view index is clamped, not branched on (a branch would make every load wait for the one before it): views
+    // past V read view V - 1 again and are masked out below
+    int rad_v[PREFETCH ? GDR_MAX_VIEWS : 1];
+    if (PREFETCH) {
+#pragma unroll
+        for (int v = 0; v < GDR_MAX_VIEWS; ++v) rad_v[v] = a.v[min(v, a.V - 1)].radii[il];
+    }
+    if (STAGED) {
+        stage_rows_store<STAGED ? ROWF : 4>(rows_in, nrows, lds_rows);
+        __syncthreads();
+    }
     float* my_row = lds_rows + (STAGED ? (int)threadIdx.x * RS::STRIDE : 0);
     if (in_range) {
     float dmean[3] = {0.f, 0.f, 0.f};
@@ -804,22 +823,23 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_views_kernel(
 #pragma unroll
     for (int k = 0; k < NB * 3; ++k) dsh[k] = 0.f;
     bool any_vis = false;
-    const float px_ = means3D[3 * i], py_ = means3D[3 * i + 1], pz_ = means3D[3 * i + 2];
-    float c6[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c6[k] = cov3D[6 * i + k];
     const float* sh_g = shs + (size_t)i * M * 3;
     auto sh = [&](int idx) -> float { return STAGED ? my_row[idx] : sh_g[idx]; };
 
-    // The gradient record of view v+1 is fetched while view v is processed: with 2 waves per SIMD (219 VGPRs) a
-    // dependent radii -> record load per view left ~3 TB/s worth of bytes in flight.
-    int n_rad = 0;
+    // The gradient record of view v+1 is fetched while view v is processed.  Which views see this Gaussian is known
+    // before the loop (rad_v above -> vis_mask), so a view's record loads wait for nothing and the only dependent load
+    // chain left in the loop is record -> arithmetic.
+    uint32_t vis_mask = 0u;
+    if (PREFETCH) {
+#pragma unroll
+        for (int v = 0; v < GDR_MAX_VIEWS; ++v)
+            if (v < a.V && rad_v[v] > 0) vis_mask |= 1u << v;
+    }
     float4 n_g2 = make_float4(0.f, 0.f, 0.f, 0.f), n_gconic = n_g2, n_gcolor = n_g2;
     uint32_t n_cl = 0u;
     auto fetch_view = [&](int v) __attribute__((always_inline)) {
         const BwdView& b = a.v[v];
-        n_rad = b.radii[i];
-        if (n_rad > 0) {
+        if ((vis_mask >> v) & 1u) {
             n_g2 = b.grad_rec[4 * i]; n_gconic = b.grad_rec[4 * i + 1]; n_gcolor = b.grad_rec[4 * i + 2];
             n_cl = b.clamped[i];
         }
@@ -827,16 +847,16 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_views_kernel(
     if (PREFETCH) fetch_view(0);
     for (int v = 0; v < a.V; ++v) {
         const BwdView& bv = a.v[v];
-        int rad;
+        bool vis;
         float4 g2, gconic, gcolor;
         uint32_t cl_v = 0u;
         if (PREFETCH) {
-            rad = n_rad; g2 = n_g2; gconic = n_gconic; gcolor = n_gcolor; cl_v = n_cl;
+            vis = (vis_mask >> v) & 1u; g2 = n_g2; gconic = n_gconic; gcolor = n_gcolor; cl_v = n_cl;
             if (v + 1 < a.V) fetch_view(v + 1);
         } else {
-            rad = bv.radii[i];
+            vis = bv.radii[i] > 0;
         }
-        if (rad <= 0) continue;
+        if (!vis) continue;
         any_vis = true;
         Cam cam;
         load_cam(cam, bv.view, bv.proj, bv.campos);
@@ -1150,8 +1170,9 @@ hipError_t launch_preprocess_bwd_views(int V, const gdr_settings* s, const gdr_i
         b.radii = radii[v]; b.clamped = geoms[v].clamped; b.grad_rec = (const float4*)grad_recs[v];
     }
     const int grid = div_up(N, GDR_BLOCK);
-    // record prefetch (see the kernel): degree 3 only — 404 -> 381 us per 4 views at 2 M Gaussians with the same 2 waves
-    // per SIMD; at degree 1 the extra registers cost a wave per SIMD (C3: 82 -> 90 us)
+    // record prefetch (see the kernel): degree 3 only, where K9 runs at 2 waves per SIMD and a view's record has to be on
+    // its way while the view before is worked on; at degree 1 the extra registers cost a wave per SIMD (136 / 130 VGPRs
+    // with it against 121 / 119 without: 3 waves instead of 4; round 5 measured C3 82 -> 90 us with it)
     static const bool prefetch = getenv("GDR_K9_PREFETCH") ? atoi(getenv("GDR_K9_PREFETCH")) != 0 : true;
 #define GDR_K9V(DEG_, ST_)                                                                                  \
     if (prefetch && V > 1 && DEG_ == 3)                                                                     \
