@@ -29,6 +29,7 @@ SEG_LEN = _int_env("GDR_SEG_LEN")          # None = policy (256; 512 on busy 800
 DEEP_MAX_BUSY = None                       # None = library default (768 busy tiles); 0 = never the deep forward
 DEEP_MIN_MEAN = _int_env("GDR_DEEP_MIN_MEAN")
 FORCE_GLOBAL_SORT = False                  # one global radix sort instead of tile partition + per-tile LDS sort (tested fallback)
+SCATTER_MODE = int(_os.environ.get("GDR_SCATTER_MODE", "0"))   # tile_scatter: 0 = the library's choice, 1 = direct stores, 2 = staged in LDS wherever a chunk fits (+ 4: linear count-matrix rows)
 FORCE_RADIX_PARTITION = False              # radix partition on the tile bits instead of the direct tile binning (tested fallback)
 LAUNCH_HINTS = True                        # launch-size feedback between calls of a scene shape
 

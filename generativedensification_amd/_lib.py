@@ -54,7 +54,7 @@ class GdrBinning(C.Structure):
                 ("seg_len", C.c_int32), ("seg_cap", C.c_int32), ("deep_max_busy", C.c_int32), ("deep_min_mean", C.c_int32),
                 ("d_dev", C.c_void_p), ("stats_out", C.c_void_p), ("hint_long", C.c_int32), ("hint_medium", C.c_int32),
                 ("hint_no_deep", C.c_int32), ("grad_rec_cleared", C.c_int32), ("tile_hist", C.c_void_p),
-                ("hist_width", C.c_int32), ("hist_tiles", C.c_int32), ("k7_class", C.c_int32), ("reserved2", C.c_int32)]
+                ("hist_width", C.c_int32), ("hist_tiles", C.c_int32), ("k7_class", C.c_int32), ("scatter_mode", C.c_int32)]
 
 
 class GdrImage(C.Structure):
@@ -197,6 +197,7 @@ _PROTOS = {
     "gdr_binning_bytes_for": (C.c_size_t, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32]),
     "gdr_binning_carve_for": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GdrBinning)]),
     "gdr_build_tag": (C.c_char_p, []),
+    "gdr_set_scatter_mode": (C.c_int32, [C.c_int32]),
     "gdr_words_differ": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "gdr_words_differ_multi": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p,
                                          C.c_void_p]),

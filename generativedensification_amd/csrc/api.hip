@@ -239,7 +239,7 @@ static size_t carve_binning(void* base, uint64_t D, gdr_binning* b, int32_t seg_
     t.hist_width = 0;
     t.hist_tiles = 0;
     t.k7_class = 0;
-    t.reserved2 = 0;
+    t.scatter_mode = 0;
     if (N > 0 && tiles > 0 && tiles <= GDR_BIN_MAX_TILES) {   // direct tile binning: (width rows x tiles) counts + a totals row
         int w = (N + 1023) / 1024;
         t.hist_width = w > GDR_BIN_MAX_WIDTH ? GDR_BIN_MAX_WIDTH : w;
@@ -348,6 +348,7 @@ int gdr_abi_version(void) { return GDR_ABI_VERSION; }
 #define GDR_BUILD_TAG "release"
 #endif
 const char* gdr_build_tag(void) { return GDR_BUILD_TAG; }
+int32_t gdr_set_scatter_mode(int32_t mode) { return set_scatter_mode_default(mode); }
 const char* gdr_last_error(void) { return g_err; }
 
 size_t gdr_geom_bytes(int32_t N) { return carve_geom(nullptr, N, nullptr); }

@@ -13,6 +13,7 @@
 // CDNA4 notes: wave = 64, so the in-wave stable ranking uses 64-bit ballots (one per
 // digit bit) instead of 32-wide match_any; LDS holds one 256-bin counter row per wave.
 #include <string.h>
+#include <atomic>
 
 #include "gdr_common.h"
 
@@ -333,8 +334,16 @@ __global__ __launch_bounds__(GDR_BLOCK) void ranges_kernel(const BinViews vs, in
 //                 column of the (tiles x workgroups) count matrix;
 //   tile_scan     exclusive scan over the workgroups in place + the tiles' totals (tile_order_kernel, the one-workgroup
 //                 kernel that follows anyway, scans the totals into the ranges: empty tiles read (0,0), as the reference's);
-//   tile_scatter  the same chunks again: LDS cursor per tile = range start + this workgroup's prefix; every rect
-//                 cell draws a position with ds_add_rtn and writes ONE 8-byte word (id << 32 | depth bits).
+//   tile_scatter  the same chunks again: every rect cell draws a position with ds_add_rtn and leaves ONE 8-byte word
+//                 (id << 32 | depth bits).  Direct: LDS cursor per tile = range start + this workgroup's prefix, the
+//                 word goes straight to its place in the list (64 lanes = up to 64 cache lines per store).  Staged
+//                 (tile_scatter_staged_kernel): the workgroup's own counts are the difference of two rows of the
+//                 scanned matrix, a scan over the tiles turns them into offsets into an LDS buffer, the words are
+//                 placed there grouped by tile and copied out with consecutive lanes on consecutive slots, so that a
+//                 tile's run leaves as one or two requests.  A chunk with more entries than the buffer holds takes the
+//                 direct route inside the same launch.  The lists only differ by a permutation within a tile.
+// Workgroup b takes chunk / matrix row (b % 8) * ceil(nwg / 8) + b / 8: the workgroups of one XCD (b % 8) own adjacent
+// rows, hence adjacent runs of every tile's list, and one L2 sees all the pieces of a line.
 // 3 launches and ~52 bytes per Gaussian + 8 per entry instead of duplicate + 2 x (hist, row scan, scatter) + ranges =
 // 8 launches and 20 + 12 + 2 x 32 + 8 bytes per entry.  Capacity-guarded like the old path (device-sized calls).
 // =================================================================================
@@ -362,13 +371,21 @@ __device__ __forceinline__ void bin_rects(const BinView& bv, int i0, int hi, int
 
 // count matrix layout: row w = workgroup w of tile_count / tile_scatter, `tstride` words (tiles rounded up to 64): every
 // access below is coalesced — the workgroups write / read their own row, the scan walks the rows with one thread per tile
+// chunk of Gaussians = row of the count matrix of this workgroup; per_xcd = ceil(nwg / 8) rows per XCD (the grid is
+// 8 * per_xcd workgroups, those beyond row nwg - 1 have nothing to do), 0 = row b for workgroup b
+__device__ __forceinline__ int bin_row(int per_xcd) {
+    return per_xcd > 0 ? (int)(blockIdx.x & 7u) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+}
+
 __global__ __launch_bounds__(GDR_BIN_THREADS) void tile_count_kernel(const BinViews vs, int N, int gx, int tiles, int chunk,
-                                                                      int tstride) {
+                                                                      int tstride, int nwg, int per_xcd) {
     const BinView& bv = vs.v[blockIdx.y];
+    const int w = bin_row(per_xcd);
+    if (w >= nwg) return;
     extern __shared__ uint32_t cnt[];
     for (int t = threadIdx.x; t < tiles; t += GDR_BIN_THREADS) cnt[t] = 0u;
     __syncthreads();
-    const int lo = blockIdx.x * chunk, hi = min(N, lo + chunk);
+    const int lo = w * chunk, hi = min(N, lo + chunk);
     for (int i0 = lo + (int)threadIdx.x; i0 < hi; i0 += GDR_BIN_BATCH * GDR_BIN_THREADS) {
         int4 r[GDR_BIN_BATCH];
         bin_rects(bv, i0, hi, r);
@@ -378,7 +395,7 @@ __global__ __launch_bounds__(GDR_BIN_THREADS) void tile_count_kernel(const BinVi
                 for (int x = r[j].x; x < r[j].z; ++x) atomicAdd(&cnt[y * gx + x], 1u);
     }
     __syncthreads();
-    uint32_t* __restrict__ row = bv.tile_hist + (size_t)blockIdx.x * tstride;
+    uint32_t* __restrict__ row = bv.tile_hist + (size_t)w * tstride;
     for (int t = threadIdx.x; t < tiles; t += GDR_BIN_THREADS) row[t] = cnt[t];
 }
 
@@ -415,17 +432,12 @@ __global__ __launch_bounds__(64 * GDR_BIN_SEGS) void tile_scan_kernel(const BinV
     if (seg == 0) bv.tile_hist[(size_t)bv.hist_width * tstride + t] = total;
 }
 
-__global__ __launch_bounds__(GDR_BIN_THREADS) void tile_scatter_kernel(const BinViews vs, int N, int gx, int tiles, int chunk,
-                                                                        int tstride) {
-    const BinView& bv = vs.v[blockIdx.y];
-    extern __shared__ uint32_t cur[];
-    const uint2* __restrict__ ranges = bv.ranges;
-    const uint32_t* __restrict__ row = bv.tile_hist + (size_t)blockIdx.x * tstride;
-    for (int t = threadIdx.x; t < tiles; t += GDR_BIN_THREADS) cur[t] = ranges[t].x + row[t];
-    __syncthreads();
-    uint64_t* __restrict__ out = bv.keys[0];
-    const uint64_t cap = bv.D;
-    const int lo = blockIdx.x * chunk, hi = min(N, lo + chunk);
+// The rect cells of a chunk, one 8-byte word each: a position from the tile's LDS cursor, then the word into `dst` if the
+// position is below `cap`.  dst = the list itself: id << 32 | depth bits.  STAGED, dst = the staging buffer: the upper half
+// is tile << 16 | (id - lo) instead (chunks of <= 65536 Gaussians, <= 16384 tiles), so that the copy-out finds the tile of
+// a slot in the word it copies.
+template <bool STAGED>
+__device__ __forceinline__ void scatter_chunk(const BinView& bv, int lo, int hi, int gx, uint32_t* cur, uint64_t* dst, uint64_t cap) {
     for (int i0 = lo + (int)threadIdx.x; i0 < hi; i0 += GDR_BIN_BATCH * GDR_BIN_THREADS) {
         int4 r[GDR_BIN_BATCH];
         uint32_t dbits[GDR_BIN_BATCH];
@@ -437,12 +449,111 @@ __global__ __launch_bounds__(GDR_BIN_THREADS) void tile_scatter_kernel(const Bin
         bin_rects(bv, i0, hi, r);
 #pragma unroll
         for (int j = 0; j < GDR_BIN_BATCH; ++j) {
-            const uint64_t word = ((uint64_t)(uint32_t)(i0 + j * GDR_BIN_THREADS) << 32) | (uint64_t)dbits[j];
+            const uint32_t id = (uint32_t)(i0 + j * GDR_BIN_THREADS);
             for (int y = r[j].y; y < r[j].w; ++y)
                 for (int x = r[j].x; x < r[j].z; ++x) {
-                    const uint32_t pos = atomicAdd(&cur[y * gx + x], 1u);
-                    if (pos < cap) out[pos] = word;   // capacity guard: never write past the caller's buffers
+                    const uint32_t t = (uint32_t)(y * gx + x);
+                    const uint32_t pos = atomicAdd(&cur[t], 1u);
+                    const uint32_t upper = STAGED ? (t << 16) | (id - (uint32_t)lo) : id;
+                    if (pos < cap) dst[pos] = ((uint64_t)upper << 32) | (uint64_t)dbits[j];   // capacity guard: never write past the buffer
                 }
+        }
+    }
+}
+
+__global__ __launch_bounds__(GDR_BIN_THREADS) void tile_scatter_kernel(const BinViews vs, int N, int gx, int tiles, int chunk,
+                                                                        int tstride, int nwg, int per_xcd) {
+    const BinView& bv = vs.v[blockIdx.y];
+    const int w = bin_row(per_xcd);
+    if (w >= nwg) return;
+    extern __shared__ uint32_t cur[];
+    const uint2* __restrict__ ranges = bv.ranges;
+    const uint32_t* __restrict__ row = bv.tile_hist + (size_t)w * tstride;
+    for (int t = threadIdx.x; t < tiles; t += GDR_BIN_THREADS) cur[t] = ranges[t].x + row[t];
+    __syncthreads();
+    const int lo = w * chunk;
+    scatter_chunk<false>(bv, lo, min(N, lo + chunk), gx, cur, bv.keys[0], bv.D);
+}
+
+// Staged scatter.  LDS: stage[stage_cap] 8-byte words | cur[tiles] | gdelta[tiles].
+//   1. this workgroup's count of tile t = (next row - own row) of the scanned matrix (the totals row for the last
+//      workgroup); a workgroup scan over the tiles gives the start of the tile's run in the staging buffer;
+//   2. placement as in the direct kernel, into the staging buffer, the tile and the chunk-local id in the word's upper half;
+//   3. copy-out: consecutive lanes take consecutive slots (GDR_BIN_COPY of a lane in flight); the word, its upper half
+//      turned back into the Gaussian id, goes to gdelta[t] + slot, gdelta[t] = range start + this workgroup's prefix -
+//      run start: the lanes of a run write adjacent addresses.
+// A chunk whose entries exceed stage_cap restores the global cursors and takes the direct route.
+#define GDR_BIN_COPY 4
+__global__ __launch_bounds__(GDR_BIN_THREADS) void tile_scatter_staged_kernel(const BinViews vs, int N, int gx, int tiles,
+                                                                               int chunk, int tstride, int nwg, int per_xcd,
+                                                                               uint32_t stage_cap) {
+    const BinView& bv = vs.v[blockIdx.y];
+    const int w = bin_row(per_xcd);
+    if (w >= nwg) return;
+    extern __shared__ uint64_t stage[];
+    __shared__ uint32_t wsum[GDR_BIN_THREADS / GDR_WAVE];
+    uint32_t* cur = (uint32_t*)(stage + stage_cap);
+    uint32_t* gdelta = cur + tiles;
+    const uint2* __restrict__ ranges = bv.ranges;
+    const uint32_t* __restrict__ row = bv.tile_hist + (size_t)w * tstride;
+    const uint32_t* __restrict__ next = bv.tile_hist + (size_t)(w + 1 < nwg ? w + 1 : bv.hist_width) * tstride;
+    for (int t = threadIdx.x; t < tiles; t += GDR_BIN_THREADS) {
+        const uint32_t r = row[t];
+        cur[t] = next[t] - r;
+        gdelta[t] = ranges[t].x + r;
+    }
+    __syncthreads();
+    const int per = (tiles + GDR_BIN_THREADS - 1) / GDR_BIN_THREADS;
+    const int t0 = min(tiles, (int)threadIdx.x * per), t1 = min(tiles, t0 + per);
+    uint32_t s = 0u;
+    for (int t = t0; t < t1; ++t) s += cur[t];
+    const uint32_t incl = wave_incl_scan(s), wv = threadIdx.x >> 6;
+    if (lane_id() == 63u) wsum[wv] = incl;
+    __syncthreads();
+    uint32_t run = incl - s, n_local = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < GDR_BIN_THREADS / GDR_WAVE; ++k) {
+        const uint32_t v = wsum[k];
+        run += k < wv ? v : 0u;
+        n_local += v;
+    }
+    const bool staged = n_local <= stage_cap;   // (the same for every thread)
+    for (int t = t0; t < t1; ++t) {
+        const uint32_t c = cur[t];
+        if (staged) {
+            cur[t] = run;
+            gdelta[t] -= run;
+        } else {
+            cur[t] = gdelta[t];
+        }
+        run += c;
+    }
+    __syncthreads();
+    const int lo = w * chunk, hi = min(N, lo + chunk);
+    uint64_t* __restrict__ out = bv.keys[0];
+    const uint64_t cap = bv.D;
+    if (!staged) {
+        scatter_chunk<false>(bv, lo, hi, gx, cur, out, cap);
+        return;
+    }
+    scatter_chunk<true>(bv, lo, hi, gx, cur, stage, (uint64_t)stage_cap);
+    __syncthreads();
+    for (uint32_t s0 = threadIdx.x; s0 < n_local; s0 += GDR_BIN_COPY * GDR_BIN_THREADS) {
+        uint64_t wd[GDR_BIN_COPY];
+        uint32_t gd[GDR_BIN_COPY];
+#pragma unroll
+        for (int j = 0; j < GDR_BIN_COPY; ++j) {
+            const uint32_t slot = s0 + (uint32_t)j * GDR_BIN_THREADS;
+            wd[j] = slot < n_local ? stage[slot] : 0ull;
+        }
+#pragma unroll
+        for (int j = 0; j < GDR_BIN_COPY; ++j) gd[j] = gdelta[(uint32_t)(wd[j] >> 48)];
+#pragma unroll
+        for (int j = 0; j < GDR_BIN_COPY; ++j) {
+            const uint32_t slot = s0 + (uint32_t)j * GDR_BIN_THREADS;
+            const uint32_t pos = gd[j] + slot;
+            const uint32_t id = (uint32_t)lo + ((uint32_t)(wd[j] >> 32) & 0xffffu);
+            if (slot < n_local && pos < cap) out[pos] = ((uint64_t)id << 32) | (wd[j] & 0xffffffffull);   // capacity guard, as in the direct kernel
         }
     }
 }
@@ -854,6 +965,15 @@ hipError_t launch_scan_block_sums(const gdr_geom* g, int N, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---- scatter_mode 0: the process-wide choice (gdr_set_scatter_mode); automatic: launch_tile_scatter decides per launch from the
+// image size and the mean entries per chunk, the staged kernel per chunk
+static std::atomic<int32_t> g_scatter_mode{GDR_SCATTER_AUTO};
+int32_t scatter_mode_default() { return g_scatter_mode.load(std::memory_order_relaxed); }
+int32_t set_scatter_mode_default(int32_t mode) {
+    if (mode < 0 || mode > (GDR_SCATTER_MODE_MASK | GDR_SCATTER_LINEAR_ROWS) || (mode & GDR_SCATTER_MODE_MASK) == 3) mode = GDR_SCATTER_AUTO;
+    return g_scatter_mode.exchange(mode, std::memory_order_relaxed);
+}
+
 // ---- BinViews table of V views ------------------------------------------------------------------------------
 void fill_bin_views(BinViews* vs, int V, const gdr_geom* geoms, const gdr_binning* bins, const gdr_image* imgs,
                     const uint64_t* D, const int32_t* const* radii) {
@@ -868,6 +988,7 @@ void fill_bin_views(BinViews* vs, int V, const gdr_geom* geoms, const gdr_binnin
         b.keys[0] = bn.keys[0]; b.keys[1] = bn.keys[1]; b.vals[0] = bn.values[0]; b.vals[1] = bn.values[1];
         b.hist = bn.hist; b.scratch32 = bn.scratch32; b.tile_hist = bn.tile_hist; b.hist_width = bn.hist_width;
         b.from_totals = 0;
+        b.scatter_mode = bn.scatter_mode != 0 ? bn.scatter_mode : scatter_mode_default();
         b.ranges = (uint2*)imgs[v].ranges; b.tile_order = imgs[v].tile_order; b.seg_base = imgs[v].seg_base;
         b.seg_extra = (uint2*)bn.seg_extra; b.seg_count = bn.seg_count;
         b.D = D[v]; b.nblk = (uint32_t)((D[v] + GDR_SORT_TILE - 1) / GDR_SORT_TILE);
@@ -936,32 +1057,69 @@ static int merged_hint(const BinViews& vs, int V, bool long_class) {
 
 // direct tile binning of V views (view = blockIdx.y; all views share N, the image size and hist_width):
 // count -> scan -> [tile_order_kernel: totals -> ranges, issued by the caller] -> scatter
-static void bin_geometry(const BinView& bv, int N, int tiles, int* nwg, int* chunk, int* tstride) {
+static void bin_geometry(const BinView& bv, int N, int tiles, int* nwg, int* chunk, int* tstride, int* per_xcd) {
     int w = div_up(N, GDR_BIN_THREADS);
     if (w > bv.hist_width) w = bv.hist_width;
     if (w < 1) w = 1;
     *chunk = div_up(div_up(N, w), GDR_BIN_THREADS) * GDR_BIN_THREADS;
     *nwg = div_up(N, *chunk);
     *tstride = div_up(tiles, 64) * 64;
+    *per_xcd = (bv.scatter_mode & GDR_SCATTER_LINEAR_ROWS) ? 0 : div_up(*nwg, 8);
 }
+static int bin_grid(int nwg, int per_xcd) { return per_xcd > 0 ? 8 * per_xcd : nwg; }
 hipError_t launch_tile_count_scan(const BinViews& vs, int V, int N, int W, int H, hipStream_t st) {
     const int gx = tile_grid_x(W), tiles = gx * tile_grid_y(H);
-    int nwg, chunk, tstride;
-    bin_geometry(vs.v[0], N, tiles, &nwg, &chunk, &tstride);
+    int nwg, chunk, tstride, per_xcd;
+    bin_geometry(vs.v[0], N, tiles, &nwg, &chunk, &tstride, &per_xcd);
     const size_t lds = (size_t)tiles * sizeof(uint32_t);
     prof_begin(GDR_K_TILE_COUNT, st);
-    hipLaunchKernelGGL(tile_count_kernel, dim3(nwg, V), dim3(GDR_BIN_THREADS), lds, st, vs, N, gx, tiles, chunk, tstride);
+    hipLaunchKernelGGL(tile_count_kernel, dim3(bin_grid(nwg, per_xcd), V), dim3(GDR_BIN_THREADS), lds, st, vs, N, gx, tiles, chunk,
+                       tstride, nwg, per_xcd);
     prof_end(GDR_K_TILE_COUNT, st);
     GDR_LAUNCH(GDR_K_TILE_SCAN, tile_scan_kernel, dim3(div_up(tiles, 64), V), dim3(64 * GDR_BIN_SEGS), st, vs, tiles, nwg, tstride);
     return hipGetLastError();
 }
+// Staging capacity (entries) of tile_scatter_staged_kernel for an image of `tiles` tiles: what the two tables leave of a
+// CU's LDS; 0 = not worth staging (the tables of a very large tile grid leave no room for runs of any length).
+#define GDR_BIN_STAGE_LDS (160 * 1024 - 256)
+#define GDR_BIN_STAGE_MIN 4096
+static uint32_t stage_capacity(int tiles, int chunk) {
+    if (chunk > 65536) return 0u;   // (the staged word holds the chunk-local id in 16 bits; such a chunk outgrows the buffer anyway)
+    const long room = (long)GDR_BIN_STAGE_LDS - 2l * tiles * (long)sizeof(uint32_t);
+    const long cap = room / (long)sizeof(uint64_t);
+    return cap >= GDR_BIN_STAGE_MIN ? (uint32_t)cap : 0u;
+}
 hipError_t launch_tile_scatter(const BinViews& vs, int V, int N, int W, int H, hipStream_t st) {
     const int gx = tile_grid_x(W), tiles = gx * tile_grid_y(H);
-    int nwg, chunk, tstride;
-    bin_geometry(vs.v[0], N, tiles, &nwg, &chunk, &tstride);
+    int nwg, chunk, tstride, per_xcd;
+    bin_geometry(vs.v[0], N, tiles, &nwg, &chunk, &tstride, &per_xcd);
+    const int mode = vs.v[0].scatter_mode & GDR_SCATTER_MODE_MASK;
+    uint32_t stage_cap = mode == GDR_SCATTER_DIRECT ? 0u : stage_capacity(tiles, chunk);
+    if (mode == GDR_SCATTER_AUTO && stage_cap > 0u) {
+        // automatic: staged only where the AVERAGE chunk fits with a tenth to spare.  Where it does not (big Gaussians on
+        // a small image), most workgroups would take the direct loop anyway and the launch would still ask for a whole
+        // CU's LDS per workgroup beside other views' K6.  (By reasoning: no measured workload is near it, EXPERIMENTS M.4.)
+        // D of a device-sized call is a capacity, 1.5 x the expected count (api.hip kDSlack, rasterizer.D_SLACK).
+        uint64_t est = 0;
+        for (int v = 0; v < V; ++v) {
+            const uint64_t d = vs.v[v].d_dev ? vs.v[v].D * 2 / 3 : vs.v[v].D;
+            est = d > est ? d : est;
+        }
+        if (est / (uint64_t)nwg > (uint64_t)stage_cap * 9 / 10) stage_cap = 0u;
+    }
+    if (stage_cap > 0u) {
+        const size_t lds = (size_t)stage_cap * sizeof(uint64_t) + 2 * (size_t)tiles * sizeof(uint32_t);
+        hipError_t e = hipFuncSetAttribute((const void*)tile_scatter_staged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        prof_begin(GDR_K_TILE_SCATTER, st);
+        hipLaunchKernelGGL(tile_scatter_staged_kernel, dim3(bin_grid(nwg, per_xcd), V), dim3(GDR_BIN_THREADS), lds, st, vs, N, gx,
+                           tiles, chunk, tstride, nwg, per_xcd, stage_cap);
+        prof_end(GDR_K_TILE_SCATTER, st);
+        return hipGetLastError();
+    }
     prof_begin(GDR_K_TILE_SCATTER, st);
-    hipLaunchKernelGGL(tile_scatter_kernel, dim3(nwg, V), dim3(GDR_BIN_THREADS), (size_t)tiles * sizeof(uint32_t), st, vs, N, gx,
-                       tiles, chunk, tstride);
+    hipLaunchKernelGGL(tile_scatter_kernel, dim3(bin_grid(nwg, per_xcd), V), dim3(GDR_BIN_THREADS), (size_t)tiles * sizeof(uint32_t),
+                       st, vs, N, gx, tiles, chunk, tstride, nwg, per_xcd);
     prof_end(GDR_K_TILE_SCATTER, st);
     return hipGetLastError();
 }

@@ -99,6 +99,7 @@ struct BinView {
     int32_t hint_long, hint_medium;   // host side only: grid sizes of the tile sort's long / medium class
     uint32_t* tile_hist; int32_t hist_width;   // direct tile binning: (hist_width rows, tiles rounded up to 64) counts + a totals row
     int32_t from_totals;                       // tile_order_kernel: ranges are formed from the totals row first
+    int32_t scatter_mode;                      // gdr_binning.scatter_mode, 0 resolved (host side only)
 };
 #define GDR_BIN_MAX_TILES 16384     // LDS histogram of the direct tile binning: 64 KB (beyond: radix partition on the tile bits)
 #define GDR_BIN_MAX_WIDTH 256       // workgroups of tile_count / tile_scatter = rows of the count matrix
@@ -106,6 +107,14 @@ struct BinView {
 #define GDR_TSORT_SMALL 2048
 #define GDR_TSORT_MEDIUM 4096
 #define GDR_TSORT_LARGE 16384
+// gdr_binning.scatter_mode
+#define GDR_SCATTER_AUTO 0
+#define GDR_SCATTER_DIRECT 1
+#define GDR_SCATTER_STAGED 2
+#define GDR_SCATTER_MODE_MASK 3
+#define GDR_SCATTER_LINEAR_ROWS 4
+int32_t scatter_mode_default();               // what scatter_mode 0 stands for (gdr_set_scatter_mode)
+int32_t set_scatter_mode_default(int32_t mode);
 struct BinViews { BinView v[GDR_MAX_VIEWS]; };
 void fill_bin_views(BinViews* vs, int V, const gdr_geom* geoms, const gdr_binning* bins, const gdr_image* imgs,
                     const uint64_t* D, const int32_t* const* radii);

@@ -268,8 +268,21 @@ class GroupMismatch(RuntimeError):
     independent node for that call)."""
 
 
+_SCATTER_MODE_SENT = [0]
+
+
+def _push_scatter_mode():
+    """K.SCATTER_MODE -> the library's process-wide tile_scatter mode (gdr_view_opts has no field for it: the entry points
+    that carve their own workspace leave gdr_binning.scatter_mode at 0 = that mode)."""
+    m = int(K.SCATTER_MODE)
+    if m != _SCATTER_MODE_SENT[0]:
+        L.load().gdr_set_scatter_mode(m)
+        _SCATTER_MODE_SENT[0] = m
+
+
 def _view_opts():
     """The test / A-B switches of this module as the library's gdr_view_opts (-1 = the library's policy)."""
+    _push_scatter_mode()
     return L.GdrViewOpts(-1 if K.SEG_LEN is None else max(0, int(K.SEG_LEN)) // 256 * 256,
                          -1 if K.DEEP_MAX_BUSY is None else max(0, int(K.DEEP_MAX_BUSY)),
                          -1 if K.DEEP_MIN_MEAN is None else max(0, int(K.DEEP_MIN_MEAN)),
@@ -278,6 +291,7 @@ def _view_opts():
 
 def view_opts_tuple():
     """_view_opts() as the six ints the compiled boundary takes."""
+    _push_scatter_mode()
     return (-1 if K.SEG_LEN is None else max(0, int(K.SEG_LEN)) // 256 * 256,
             -1 if K.DEEP_MAX_BUSY is None else max(0, int(K.DEEP_MAX_BUSY)),
             -1 if K.DEEP_MIN_MEAN is None else max(0, int(K.DEEP_MIN_MEAN)),
@@ -771,6 +785,7 @@ def _carve_binning(lib, st, entries, tiles, d_dev=None, stats=None, hints=None):
     if K.FORCE_RADIX_PARTITION:
         st.bin.tile_hist, st.bin.hist_width = None, 0
     st.bin.global_sort = int(K.FORCE_GLOBAL_SORT)
+    st.bin.scatter_mode = int(K.SCATTER_MODE)
     st.bin.d_dev = d_dev
     st.D = entries
     if K.DEEP_MAX_BUSY is not None:

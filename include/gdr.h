@@ -192,7 +192,11 @@ typedef struct gdr_binning {
     int32_t k7_class;    /* v16: duplicates per Gaussian of the view as a quarter-octave class (1..63), set by gdr_forward_view(s)
                           * from the exact count; 0 = unknown.  Part of the key under which the library remembers which K7
                           * serves a scene (gdr_k7_tune_*) — nothing else reads it */
-    int32_t reserved2;
+    int32_t scatter_mode;/* how tile_scatter writes the partitioned lists (same lists up to the order within a tile, which the per-tile
+                          * sort removes): 0 = the library's choice (gdr_set_scatter_mode), 1 = direct, one store per entry
+                          * straight into the list, 2 = staged in LDS and written out in runs wherever a workgroup's entries
+                          * fit the staging buffer; + 4: count-matrix row = workgroup index instead of the XCD-contiguous
+                          * map (measurement).  The carve functions set 0.  (The field was named reserved2.) */
 } gdr_binning;
 
 /* Image state (upstream "imgBuffer"). */
@@ -243,6 +247,10 @@ const char* gdr_last_error(void); /* thread-local, host string */
 /* "release" for the product build.  Anything else marks a measurement / experimental build of the library (compiled with
  * -DGDR_BUILD_TAG=...): the Python loader refuses to load such a library unless GDR_ALLOW_EXPERIMENTAL_LIB=1 is set. */
 const char* gdr_build_tag(void);
+/* Process-wide tile_scatter mode for every gdr_binning whose scatter_mode is 0 (the entry points that carve their own
+ * workspace: gdr_forward_view(s), gsr_forward_view): the values of gdr_binning.scatter_mode; 0 = automatic.  Returns the
+ * previous value. */
+int32_t gdr_set_scatter_mode(int32_t mode);
 
 size_t gdr_geom_bytes(int32_t N);
 size_t gdr_binning_bytes(uint64_t D);
