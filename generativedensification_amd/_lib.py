@@ -179,6 +179,9 @@ GDR_SEG_ROWS, GDR_SEG_MAX_CHANNELS = 32, 65536
 GDR_SEG_DTYPES = {"f16": 0, "bf16": 1, "f32": 2, "i64": 3}
 GDR_SEG_OPS = {"sum": 0, "mean": 1, "min": 2, "max": 3}
 
+GDR_NORM_DTYPES = {"f16": 0, "bf16": 1, "f32": 2}
+GDR_NORM_ROWS, GDR_NORM_MAX_CHANNELS, GDR_NORM_MAX_SEGMENTS, GDR_NORM_MAX_FREQS, GDR_NORM_MAX_UPSCALE = 32, 1024, 1024, 16, 16
+
 
 class GdrSubmArgs(C.Structure):   # include/gdr.h gdr_subm_args
     _fields_ = [("N", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("K", C.c_int32), ("dtype", C.c_int32),
@@ -334,6 +337,16 @@ _PROTOS = {
                                  C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gdr_seg_route": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gdr_seg_ptr_from_sorted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gdr_norm_ada_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                       C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_norm_ada_backward_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gdr_norm_ada_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 3 + [C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                                        C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_norm_pe_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "gdr_norm_pe_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                       C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

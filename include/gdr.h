@@ -824,6 +824,50 @@ int gdr_seg_route(const void* grad_out, const int64_t* arg, int64_t N, int64_t S
                   void* stream);
 int gdr_seg_ptr_from_sorted(const int64_t* index, const int64_t* perm, int64_t N, int64_t S, int64_t* indptr, void* stream);
 
+/* ---- fused row normalisations of the point decoder (csrc/norm.hip; added in v17, backward-compatible) ----------------------
+ * ada: the reference's AdaLayerNorm, out[i] = scale[b] * layer_norm(feat[i]) for row i of segment b; pe: the input of
+ * UpscaleModule.delta_f, layer_norm([sin(f x), cos(f x), feat of the parent]).  The arithmetic is restated in the header of
+ * csrc/norm.hip.  The caller owns every buffer; all are device memory.  Every `*_dtype` is one of GDR_NORM_F16 / BF16 / F32
+ * and the types of one call are independent; the arithmetic is f32.  Refusals happen before any launch; N = 0 / P = 0 return
+ * GDR_OK without one; no entry point allocates or synchronises with the host.  No atomics: two runs are bitwise equal.
+ * Envelope (GDR_ERR_UNSUPPORTED beyond it): C a multiple of 8 in 8..GDR_NORM_MAX_CHANNELS, 1 <= B <= GDR_NORM_MAX_SEGMENTS,
+ * 1 <= F <= GDR_NORM_MAX_FREQS, 1 <= S <= GDR_NORM_MAX_UPSCALE, N and P * S below 2^31.
+ * Rows: "rows of X" below means a 16-byte aligned base and a row stride (in elements) that is a multiple of 8 and >= the row.
+ *
+ * ada_forward: rows of feat (N, C) and scale (B, C); offset: B int64, the inclusive segment ends (non-decreasing; values are
+ *   clamped to [0, N] where they are read); out (N, C) dense, 16-byte aligned, of out_dtype.  Rows at or behind offset[B - 1]
+ *   are written as zeros.  1 launch.
+ * ada_backward: grad_out: rows of (N, C) of grad_dtype.  grad_feat (N, C) dense of feat_dtype, grad_scale (B, C) dense of
+ *   scale_dtype, both 16-byte aligned and written whole (rows behind the last end and empty segments get zeros).  mean and rstd
+ *   are recomputed.  workspace: gdr_norm_ada_backward_bytes(N, B, C) bytes, 256-byte aligned.  2 launches.
+ * pe_forward: x (P * S, 3) dense; rows of feat (P, C); freq: F values; out: rows of (P * S, 6 F + C) through out_stride; the
+ *   elements of a row behind 6 F + C up to the next multiple of 8 are written as zeros.  1 launch.
+ * pe_backward: grad_out (P * S, 6 F + C) through grad_stride, which must be even, from a base aligned to two elements (a
+ *   16-byte base and a stride that is a multiple of 8 take the wide path).  grad_x (P * S, 3) dense of x_dtype, grad_feat
+ *   (P, C) dense of feat_dtype, 16-byte aligned; a NULL output is not wanted.  1 launch. */
+#define GDR_NORM_F16 0
+#define GDR_NORM_BF16 1
+#define GDR_NORM_F32 2
+#define GDR_NORM_ROWS 32               /* rows per workgroup of the ada backward: one dscale partial pair per that many rows */
+#define GDR_NORM_MAX_CHANNELS 1024
+#define GDR_NORM_MAX_SEGMENTS 1024
+#define GDR_NORM_MAX_FREQS 16
+#define GDR_NORM_MAX_UPSCALE 16
+int gdr_norm_ada_forward(const void* feat, int64_t feat_stride, int32_t feat_dtype, const void* scale, int64_t scale_stride,
+                         int32_t scale_dtype, const int64_t* offset, int64_t N, int32_t B, int32_t C, float eps, void* out,
+                         int32_t out_dtype, void* stream);
+size_t gdr_norm_ada_backward_bytes(int64_t N, int32_t B, int32_t C);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_norm_ada_backward(const void* grad_out, int64_t grad_stride, int32_t grad_dtype, const void* feat, int64_t feat_stride,
+                          int32_t feat_dtype, const void* scale, int64_t scale_stride, int32_t scale_dtype, const int64_t* offset,
+                          int64_t N, int32_t B, int32_t C, float eps, void* workspace, size_t workspace_bytes, void* grad_feat,
+                          void* grad_scale, void* stream);
+int gdr_norm_pe_forward(const void* x, int32_t x_dtype, const void* feat, int64_t feat_stride, int32_t feat_dtype, const void* freq,
+                        int32_t freq_dtype, int64_t P, int32_t S, int32_t C, int32_t F, float eps, void* out, int64_t out_stride,
+                        int32_t out_dtype, void* stream);
+int gdr_norm_pe_backward(const void* grad_out, int64_t grad_stride, int32_t grad_dtype, const void* x, int32_t x_dtype,
+                         const void* feat, int64_t feat_stride, int32_t feat_dtype, const void* freq, int32_t freq_dtype, int64_t P,
+                         int32_t S, int32_t C, int32_t F, float eps, void* grad_x, void* grad_feat, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
