@@ -30,8 +30,19 @@ DEEP_MAX_BUSY = None                       # None = library default (768 busy ti
 DEEP_MIN_MEAN = _int_env("GDR_DEEP_MIN_MEAN")
 FORCE_GLOBAL_SORT = False                  # one global radix sort instead of tile partition + per-tile LDS sort (tested fallback)
 SCATTER_MODE = int(_os.environ.get("GDR_SCATTER_MODE", "0"))   # tile_scatter: 0 = the library's choice, 1 = direct stores, 2 = staged in LDS wherever a chunk fits (+ 4: linear count-matrix rows)
+TILE_SORT_MODE = int(_os.environ.get("GDR_TILE_SORT_MODE", "0"))   # per-tile depth sort of lists <= 4096: 0 = the library's choice (bucket), 1 = radix passes + tie pass, 2 = bucket pass + in-bucket fix-up (radix where a bucket overfills)
 FORCE_RADIX_PARTITION = False              # radix partition on the tile bits instead of the direct tile binning (tested fallback)
 LAUNCH_HINTS = True                        # launch-size feedback between calls of a scene shape
 
 # ---- the duplicate count --------------------------------------------------------------------------------------------------
 DEFER_D = _os.environ.get("GDR_DEFER_D", "1") != "0"   # False: read the count back before sizing anything (upstream's flow)
+
+
+def tile_sort_fallbacks(reset=True):
+    """Lists that left the tile sort's bucket path for the radix code since the counter was last cleared (current device;
+    waits for the device).  Debug only: the tests use it to see which path a tile took."""
+    from . import _lib
+    n = int(_lib.load().gdr_debug_tile_sort_fallbacks(1 if reset else 0))
+    if n < 0:
+        raise RuntimeError("gdr_debug_tile_sort_fallbacks failed")
+    return n

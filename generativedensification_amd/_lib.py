@@ -201,6 +201,8 @@ _PROTOS = {
     "gdr_binning_carve_for": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GdrBinning)]),
     "gdr_build_tag": (C.c_char_p, []),
     "gdr_set_scatter_mode": (C.c_int32, [C.c_int32]),
+    "gdr_set_tile_sort_mode": (C.c_int32, [C.c_int32]),
+    "gdr_debug_tile_sort_fallbacks": (C.c_int64, [C.c_int32]),
     "gdr_words_differ": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "gdr_words_differ_multi": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p,
                                          C.c_void_p]),

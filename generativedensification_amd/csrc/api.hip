@@ -349,6 +349,8 @@ int gdr_abi_version(void) { return GDR_ABI_VERSION; }
 #endif
 const char* gdr_build_tag(void) { return GDR_BUILD_TAG; }
 int32_t gdr_set_scatter_mode(int32_t mode) { return set_scatter_mode_default(mode); }
+int32_t gdr_set_tile_sort_mode(int32_t mode) { return set_tile_sort_mode_default(mode); }
+int64_t gdr_debug_tile_sort_fallbacks(int32_t reset) { return tile_sort_fallbacks(reset); }
 const char* gdr_last_error(void) { return g_err; }
 
 size_t gdr_geom_bytes(int32_t N) { return carve_geom(nullptr, N, nullptr); }

@@ -562,16 +562,21 @@ __global__ __launch_bounds__(GDR_BIN_THREADS) void tile_scatter_staged_kernel(co
 // Tile-binned sort (default path).  The sort key is (tile, depth).  Instead of 6 global radix
 // passes over the 12-byte pairs, the pairs are first partitioned by TILE with the stable
 // passes above run on the tile bits only (2 passes at 800x800), K5 reads the tile segments off
-// the partitioned keys, and then ONE workgroup per tile sorts its segment by depth in LDS with
-// a stable 8-bit LSD radix sort on (depth - min depth of the tile): typically 3 passes, no
-// global traffic besides one read and one write of the segment.  Entries with identical depth
-// bits are finally put in ascending Gaussian-id order, which is exactly what the reference's
-// single global stable sort of Gaussian-ordered duplicates yields => bit-identical sorted list.  A segment longer than the LDS capacity is sorted
-// by its workgroup with the same code on the global ping-pong buffers.
+// the partitioned keys, and then ONE workgroup per tile sorts its segment in LDS by (depth bits,
+// Gaussian id), no global traffic besides one read and one write of the segment.  That order is
+// exactly what the reference's single global stable sort of Gaussian-ordered duplicates yields
+// => bit-identical sorted list; a Gaussian occurs once per tile, so the composite key is unique
+// and any correct sort gives it.  Two ways to get there:
+//   bucket (lists <= 4096, the default): one counting pass on 4096 buckets of (depth - min depth
+//     of the tile), then every entry ranks itself inside its bucket (comment at tile_sort_kernel);
+//   radix  (longer lists; a list with an overfull bucket; gdr_set_tile_sort_mode(1)): stable 8-bit
+//     LSD passes on (depth - min depth), typically 3, then entries with identical depth bits are
+//     put in ascending id order (tile_sort_ties).  A segment longer than the LDS capacity is sorted
+//     by its workgroup with the same code on the global ping-pong buffers.
 // =================================================================================
 // three size classes so that LDS footprint (= workgroups per CU) follows the list length:
-//   short  (L <= 2048): 20 KiB, 4 waves, one workgroup per tile;
-//   medium (L <= 4096): 40 KiB, 8 waves   } small grids that walk the tiles longest-first
+//   short  (L <= 2048): 25 KiB, 4 waves, one workgroup per tile (8 KiB of it the bucket counters; 21 KiB before them);
+//   medium (L <= 4096): 41 KiB, 8 waves   } small grids that walk the tiles longest-first
 //   long   (L <= 16384 in LDS, beyond that on the global ping-pong buffers): 144 KiB, 16 waves, 16 elements per lane }
 //          (8192 / 80 KiB until object-like scenes were measured: their 10-19 k-entry lists took the global route; C4 shell
 //          963 -> 991, C3 shell 3120 -> 3210, uniform scenes unchanged)
@@ -795,8 +800,27 @@ __device__ __forceinline__ void tile_sort_ties(const uint32_t* kA, uint32_t* vA,
 // PACKED: the partitioned list is one word per entry, (id << 32) | depth bits (direct tile binning); otherwise keys
 // (tile << 32 | depth bits) + values in two arrays (radix partition).  Output: the sorted ids only — the sorted keys are
 // a function of (ranges, ids, depths) and nothing downstream reads them (the parity tests rebuild them from those).
+//
+// Bucket path (lists of the short and medium class, CAP <= GDR_TSORT_MEDIUM; `bucket` = the mode allows it): the order asked for
+// is ascending (depth bits, Gaussian id), a Gaussian occurs once per tile, so the composite key is unique and ANY correct
+// sort gives the same list — stability buys nothing.  One counting pass on a monotone map of the depth onto
+// GDR_TSORT_BUCKETS buckets, b = (key - kmin) >> max(0, bits(kmax - kmin) - 12), places every element in its bucket's span
+// (arrival order inside a bucket arbitrary), then the entry at every slot counts the entries of its bucket that precede it
+// in (key, id) and its id is stored at bucket start + rank.  Counters: 16 bits each, two per LDS word, shared by
+// the workgroup (counts and span starts are <= 4096, a half never carries into the other).  If one bucket holds more than
+// GDR_TSORT_BUCKET_MAX elements (depths clustered on a surface, a plane seen head-on) the workgroup takes the radix + ties
+// code instead: decided before anything is placed, uniform over the workgroup.
+#define GDR_TSORT_BUCKETS 4096
+#define GDR_TSORT_BUCKET_MAX 16
+// debug only (gdr_debug_tile_sort_fallbacks, tests): lists that tried the bucket path and took the radix code instead.
+// 32 slots a cache line apart, picked by workgroup, so that a scene whose every tile falls back does not queue on one word.
+#define GDR_TSORT_FB_SLOTS 32
+__device__ uint32_t g_tsort_fallbacks[GDR_TSORT_FB_SLOTS * 16];
+
 template <int CAP, int LMIN, int NW, bool TOP, bool PACKED>
-__global__ __launch_bounds__(NW * GDR_WAVE) void tile_sort_kernel(const BinViews vs, int in, int ntiles) {
+// (second bound: the 4-wave short class keeps the 5 waves per SIMD = 5 workgroups per CU it had before the bucket path; for the
+// 8- and 16-wave classes 4 and 5 waves per SIMD hold the same 2 / 1 workgroups)
+__global__ __launch_bounds__(NW * GDR_WAVE, NW == 4 ? 5 : 4) void tile_sort_kernel(const BinViews vs, int in, int ntiles, int bucket) {
     const BinView& bv = vs.v[blockIdx.y];
     const uint2* __restrict__ ranges = bv.ranges;
     const uint64_t* __restrict__ keys_part = bv.keys[in];
@@ -808,7 +832,13 @@ __global__ __launch_bounds__(NW * GDR_WAVE) void tile_sort_kernel(const BinViews
     if (view_D(bv) == 0) return;
     constexpr uint32_t NT = NW * GDR_WAVE;
     __shared__ uint32_t lds_elems[2 * CAP];   // (depth key, id) of a list of <= CAP entries, sorted in place
-    __shared__ uint32_t cnt[NW][GDR_RADIX];
+    // radix: cnt[NW][256] per-wave digit counters; bucket path: GDR_TSORT_BUCKETS 16-bit counters, two per word (8 KB)
+    constexpr bool BUCKET = CAP <= GDR_TSORT_MEDIUM;
+    constexpr int BWORDS = GDR_TSORT_BUCKETS / 2;
+    constexpr int CNT_WORDS = (BUCKET && NW * GDR_RADIX < BWORDS) ? BWORDS : NW * GDR_RADIX;
+    __shared__ uint32_t cnt_words[CNT_WORDS];
+    uint32_t (*const cnt)[GDR_RADIX] = reinterpret_cast<uint32_t (*)[GDR_RADIX]>(cnt_words);
+    __shared__ uint32_t bsc[2 * NW];   // bucket path: per-wave element totals, per-wave largest bucket
     __shared__ uint32_t misc[8];
     __shared__ uint32_t mm[2 * NW];
     __shared__ uint32_t bstart[TOP ? GDR_RADIX + 1 : 1];
@@ -834,14 +864,127 @@ __global__ __launch_bounds__(NW * GDR_WAVE) void tile_sort_kernel(const BinViews
         uint32_t* const kA = lds_elems;
         uint32_t* const vA = lds_elems + CAP;
         uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
-        for (uint32_t i = threadIdx.x; i < Lc; i += NT) {
-            const uint32_t k = key_at(i);
-            kA[i] = k;
-            vA[i] = val_at(i);
-            kmin = min(kmin, k);
-            kmax = max(kmax, k);
+        bool in_lds = false;
+        if constexpr (BUCKET) {
+            if (bucket) {   // (uniform over the grid)
+                constexpr int WPT = BWORDS / (int)NT;   // counter words per thread: 2 * WPT consecutive buckets
+                uint32_t key[EPT], val[EPT];
+#pragma unroll
+                for (int j = 0; j < EPT; ++j) {
+                    const uint32_t i = threadIdx.x + (uint32_t)j * NT;
+                    const bool valid = i < Lc;
+                    key[j] = valid ? key_at(i) : 0u;
+                    val[j] = valid ? val_at(i) : 0u;
+                    if (valid) { kmin = min(kmin, key[j]); kmax = max(kmax, key[j]); }
+                }
+#pragma unroll
+                for (int k = 0; k < WPT; ++k) cnt_words[threadIdx.x + (uint32_t)k * NT] = 0u;
+                min_max(kmin, kmax);   // (its barrier: the counters are clear from here on)
+                const uint32_t span = kmax - kmin;
+                const int nbits = span ? 32 - __builtin_clz(span) : 0;
+                const int bshift = nbits > 12 ? nbits - 12 : 0;
+#pragma unroll
+                for (int j = 0; j < EPT; ++j) {
+                    const uint32_t b = (key[j] - kmin) >> bshift;
+                    if (threadIdx.x + (uint32_t)j * NT < Lc) atomicAdd(&cnt_words[b >> 1], 1u << ((b & 1u) * 16u));
+                }
+                __syncthreads();
+                uint32_t cw[WPT], sum = 0u, big = 0u;
+#pragma unroll
+                for (int k = 0; k < WPT; ++k) {
+                    cw[k] = cnt_words[threadIdx.x * WPT + k];
+                    const uint32_t c0 = cw[k] & 0xFFFFu, c1 = cw[k] >> 16;
+                    sum += c0 + c1;
+                    big = max(big, max(c0, c1));
+                }
+                const uint32_t incl = wave_incl_scan(sum);
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) big = max(big, (uint32_t)__shfl_xor((int)big, off, 64));
+                if (lane == 63) bsc[w] = incl;
+                if (lane == 0) bsc[NW + w] = big;
+                __syncthreads();
+                uint32_t base = incl - sum;
+                for (uint32_t k = 0; k < (uint32_t)NW; ++k) {
+                    if (k < w) base += bsc[k];
+                    big = max(big, bsc[NW + k]);
+                }
+                if (big <= (uint32_t)GDR_TSORT_BUCKET_MAX) {   // (uniform over the workgroup)
+                    uint32_t s = base;   // counters -> where each bucket's span starts (both halves stay <= Lc: no carry)
+#pragma unroll
+                    for (int k = 0; k < WPT; ++k) {
+                        const uint32_t c0 = cw[k] & 0xFFFFu, c1 = cw[k] >> 16;
+                        cnt_words[threadIdx.x * WPT + k] = s | ((s + c0) << 16);
+                        s += c0 + c1;
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int j = 0; j < EPT; ++j) {   // (the list lives in registers: nothing in kA / vA is still to be read)
+                        const uint32_t b = (key[j] - kmin) >> bshift, sh = (b & 1u) * 16u;
+                        if (threadIdx.x + (uint32_t)j * NT < Lc) {
+                            const uint32_t slot = (atomicAdd(&cnt_words[b >> 1], 1u << sh) >> sh) & 0xFFFFu;
+                            kA[slot] = key[j];
+                            vA[slot] = val[j];
+                        }
+                    }
+                    __syncthreads();
+                    // every counter now holds where its bucket ENDS = where the next one starts.  Fix-up by RANKING, one
+                    // thread per slot: the entry at slot i counts the entries of its bucket that precede it in (key, id)
+                    // and its id goes straight to global memory at (bucket start + rank) — nothing is moved in LDS, no
+                    // further barrier.  The loop runs to the largest bucket a wave meets (<= GDR_TSORT_BUCKET_MAX) and
+                    // issues the reads of all EPT slots of a lane together.  (A lane that owns 16 consecutive buckets and
+                    // insertion-sorts them was measured first: some lane of a wave finds a bucket of two in nearly every
+                    // one of the 16 steps, so every wave paid 16 dependent insertion sorts — short class 27 -> 38 us.)
+                    const uint16_t* const ends = reinterpret_cast<const uint16_t*>(cnt_words);
+                    uint32_t pos[EPT], lim[EPT], rank[EPT];
+#pragma unroll
+                    for (int j = 0; j < EPT; ++j) {   // (key / val: from here on the entry at slot i)
+                        const uint32_t i = threadIdx.x + (uint32_t)j * NT;
+                        const bool valid = i < Lc;
+                        key[j] = valid ? kA[i] : kmin;
+                        val[j] = valid ? vA[i] : 0u;
+                        const uint32_t b = (key[j] - kmin) >> bshift;
+                        const uint32_t e = valid ? ends[b] : 0u;
+                        pos[j] = (valid && b > 0u) ? ends[b - 1u] : 0u;
+                        lim[j] = e - pos[j] >= 2u && valid ? e : pos[j];   // (alone in its bucket: nothing to rank)
+                        rank[j] = 0u;
+                    }
+                    for (uint32_t t = 0; t < (uint32_t)GDR_TSORT_BUCKET_MAX; ++t) {
+                        bool more = false;
+#pragma unroll
+                        for (int j = 0; j < EPT; ++j) {   // (unconditional reads, slot 0 where there is nothing to compare: the
+                            const bool in = pos[j] + t < lim[j];   //  16 reads of a step leave together, one wait)
+                            const uint32_t q = in ? pos[j] + t : 0u;
+                            const uint32_t kq = kA[q], vq = vA[q];
+                            rank[j] += (in && (kq < key[j] || (kq == key[j] && vq < val[j]))) ? 1u : 0u;
+                            more = more || in;
+                        }
+                        if (!__any(more)) break;
+                    }
+#pragma unroll
+                    for (int j = 0; j < EPT; ++j)
+                        if (threadIdx.x + (uint32_t)j * NT < Lc) vals_out[o + pos[j] + rank[j]] = val[j];
+                    return;
+                }
+                // one bucket too full: the radix + ties code below on the untouched list
+                if (threadIdx.x == 0) atomicAdd(&g_tsort_fallbacks[(blockIdx.x % GDR_TSORT_FB_SLOTS) * 16], 1u);
+#pragma unroll
+                for (int j = 0; j < EPT; ++j) {
+                    const uint32_t i = threadIdx.x + (uint32_t)j * NT;
+                    if (i < Lc) { kA[i] = key[j]; vA[i] = val[j]; }
+                }
+                in_lds = true;   // (kmin / kmax are the workgroup's already; every pass and the tie pass open with a barrier)
+            }
         }
-        min_max(kmin, kmax);
+        if (!in_lds) {
+            for (uint32_t i = threadIdx.x; i < Lc; i += NT) {
+                const uint32_t k = key_at(i);
+                kA[i] = k;
+                vA[i] = val_at(i);
+                kmin = min(kmin, k);
+                kmax = max(kmax, k);
+            }
+            min_max(kmin, kmax);
+        }
         const uint32_t span = kmax - kmin;
         const int nbits = span ? 32 - __builtin_clz(span) : 0;
         for (int shift = 0; shift < nbits; shift += GDR_RADIX_BITS)
@@ -972,6 +1115,27 @@ int32_t scatter_mode_default() { return g_scatter_mode.load(std::memory_order_re
 int32_t set_scatter_mode_default(int32_t mode) {
     if (mode < 0 || mode > (GDR_SCATTER_MODE_MASK | GDR_SCATTER_LINEAR_ROWS) || (mode & GDR_SCATTER_MODE_MASK) == 3) mode = GDR_SCATTER_AUTO;
     return g_scatter_mode.exchange(mode, std::memory_order_relaxed);
+}
+
+// ---- tile sort mode (gdr_set_tile_sort_mode): how the short and medium class sort a list; 0 = automatic = bucket
+static std::atomic<int32_t> g_tile_sort_mode{GDR_TSORT_AUTO};
+int32_t tile_sort_mode_default() { return g_tile_sort_mode.load(std::memory_order_relaxed); }
+int32_t set_tile_sort_mode_default(int32_t mode) {
+    if (mode < 0 || mode > GDR_TSORT_BUCKET) mode = GDR_TSORT_AUTO;
+    return g_tile_sort_mode.exchange(mode, std::memory_order_relaxed);
+}
+// debug only: waits for the device, sums (and, reset != 0, clears) the current device's fallback counters; < 0: a HIP error
+int64_t tile_sort_fallbacks(int32_t reset) {
+    uint32_t h[GDR_TSORT_FB_SLOTS * 16];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tsort_fallbacks), sizeof(h)) != hipSuccess) return -1;
+    int64_t n = 0;
+    for (int k = 0; k < GDR_TSORT_FB_SLOTS; ++k) n += h[k * 16];
+    if (reset) {
+        memset(h, 0, sizeof(h));
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_tsort_fallbacks), h, sizeof(h)) != hipSuccess) return -1;
+    }
+    return n;
 }
 
 // ---- BinViews table of V views ------------------------------------------------------------------------------
@@ -1134,6 +1298,7 @@ hipError_t launch_tile_scatter(const BinViews& vs, int V, int N, int W, int H, h
 #endif
 hipError_t launch_tile_sort_views(const BinViews& vs, int V, int in, int tiles, bool packed, hipStream_t st) {
     if (max_D(vs, V) == 0) return hipSuccess;
+    const int bucket = tile_sort_mode_default() != GDR_TSORT_RADIX ? 1 : 0;   // (automatic = bucket)
     // long lists: 16 waves per workgroup so that the few heavy tiles finish quickly; a two-class scheme (everything
     // beyond the short class bucketed and sorted in short-class chunks) measured slower at 2 M - 8 M Gaussians and equal
     // at 32 M; medium and long merged into one 16-wave class: C4 1251 -> 1231, C3 2924 -> 2897, shells +1 %; short and
@@ -1158,23 +1323,23 @@ hipError_t launch_tile_sort_views(const BinViews& vs, int V, int in, int tiles, 
     if (packed) {
         if (!no_long)
             GDR_LAUNCH(GDR_K_TILE_SORT_LONG, (tile_sort_kernel<GDR_TSORT_LARGE, GDR_TSORT_MEDIUM, 16, true, true>),
-                       dim3(g_long, V), dim3(16 * GDR_WAVE), st, vs, in, tiles);
+                       dim3(g_long, V), dim3(16 * GDR_WAVE), st, vs, in, tiles, bucket);
         if (no_long)
             GDR_LAUNCH(GDR_K_TILE_SORT_LONG, (tile_sort_kernel<GDR_TSORT_MEDIUM, GDR_TSORT_SMALL, MW, true, true>),
-                       dim3(g_medium, V), dim3(MW * GDR_WAVE), st, vs, in, tiles);
+                       dim3(g_medium, V), dim3(MW * GDR_WAVE), st, vs, in, tiles, bucket);
         else
             GDR_LAUNCH(GDR_K_TILE_SORT_LONG, (tile_sort_kernel<GDR_TSORT_MEDIUM, GDR_TSORT_SMALL, MW, false, true>),
-                       dim3(g_medium, V), dim3(MW * GDR_WAVE), st, vs, in, tiles);
+                       dim3(g_medium, V), dim3(MW * GDR_WAVE), st, vs, in, tiles, bucket);
         GDR_LAUNCH(GDR_K_TILE_SORT, (tile_sort_kernel<GDR_TSORT_SMALL, 0, 4, false, true>), dim3(tiles, V), dim3(GDR_BLOCK), st,
-                   vs, in, tiles);
+                   vs, in, tiles, bucket);
         return hipGetLastError();
     }
     GDR_LAUNCH(GDR_K_TILE_SORT_LONG, (tile_sort_kernel<GDR_TSORT_LARGE, GDR_TSORT_MEDIUM, 16, true, false>),
-               dim3(g_long, V), dim3(16 * GDR_WAVE), st, vs, in, tiles);
+               dim3(g_long, V), dim3(16 * GDR_WAVE), st, vs, in, tiles, bucket);
     GDR_LAUNCH(GDR_K_TILE_SORT_LONG, (tile_sort_kernel<GDR_TSORT_MEDIUM, GDR_TSORT_SMALL, 8, false, false>),
-               dim3(g_medium, V), dim3(8 * GDR_WAVE), st, vs, in, tiles);
+               dim3(g_medium, V), dim3(8 * GDR_WAVE), st, vs, in, tiles, bucket);
     GDR_LAUNCH(GDR_K_TILE_SORT, (tile_sort_kernel<GDR_TSORT_SMALL, 0, 4, false, false>), dim3(tiles, V), dim3(GDR_BLOCK), st, vs,
-               in, tiles);
+               in, tiles, bucket);
     return hipGetLastError();
 }
 

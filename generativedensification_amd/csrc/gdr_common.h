@@ -115,6 +115,13 @@ struct BinView {
 #define GDR_SCATTER_LINEAR_ROWS 4
 int32_t scatter_mode_default();               // what scatter_mode 0 stands for (gdr_set_scatter_mode)
 int32_t set_scatter_mode_default(int32_t mode);
+// gdr_set_tile_sort_mode: how the tile sort's short and medium class sort a list (the long class and the global route: radix)
+#define GDR_TSORT_AUTO 0     /* = bucket */
+#define GDR_TSORT_RADIX 1    /* stable 8-bit LSD passes + tie pass */
+#define GDR_TSORT_BUCKET 2   /* one counting pass on 4096 depth buckets + in-bucket fix-up; radix where a bucket overfills */
+int32_t tile_sort_mode_default();
+int32_t set_tile_sort_mode_default(int32_t mode);
+int64_t tile_sort_fallbacks(int32_t reset);   // debug: lists that left the bucket path for the radix code (current device)
 struct BinViews { BinView v[GDR_MAX_VIEWS]; };
 void fill_bin_views(BinViews* vs, int V, const gdr_geom* geoms, const gdr_binning* bins, const gdr_image* imgs,
                     const uint64_t* D, const int32_t* const* radii);

@@ -269,15 +269,21 @@ class GroupMismatch(RuntimeError):
 
 
 _SCATTER_MODE_SENT = [0]
+_TILE_SORT_MODE_SENT = [0]
 
 
 def _push_scatter_mode():
     """K.SCATTER_MODE -> the library's process-wide tile_scatter mode (gdr_view_opts has no field for it: the entry points
-    that carve their own workspace leave gdr_binning.scatter_mode at 0 = that mode)."""
+    that carve their own workspace leave gdr_binning.scatter_mode at 0 = that mode), and K.TILE_SORT_MODE -> the
+    process-wide mode of the per-tile depth sort."""
     m = int(K.SCATTER_MODE)
     if m != _SCATTER_MODE_SENT[0]:
         L.load().gdr_set_scatter_mode(m)
         _SCATTER_MODE_SENT[0] = m
+    m = int(K.TILE_SORT_MODE)
+    if m != _TILE_SORT_MODE_SENT[0]:     # K.TILE_SORT_MODE -> gdr_set_tile_sort_mode, the same way
+        L.load().gdr_set_tile_sort_mode(m)
+        _TILE_SORT_MODE_SENT[0] = m
 
 
 def _view_opts():
@@ -786,6 +792,7 @@ def _carve_binning(lib, st, entries, tiles, d_dev=None, stats=None, hints=None):
         st.bin.tile_hist, st.bin.hist_width = None, 0
     st.bin.global_sort = int(K.FORCE_GLOBAL_SORT)
     st.bin.scatter_mode = int(K.SCATTER_MODE)
+    _push_scatter_mode()     # (K.TILE_SORT_MODE has no gdr_binning field: process-wide only)
     st.bin.d_dev = d_dev
     st.D = entries
     if K.DEEP_MAX_BUSY is not None:

@@ -251,6 +251,13 @@ const char* gdr_build_tag(void);
  * workspace: gdr_forward_view(s), gsr_forward_view): the values of gdr_binning.scatter_mode; 0 = automatic.  Returns the
  * previous value. */
 int32_t gdr_set_scatter_mode(int32_t mode);
+/* Process-wide mode of the per-tile depth sort for lists of up to 4096 entries (longer lists are not affected): 0 = automatic
+ * (= 2), 1 = stable 8-bit radix passes + tie pass, 2 = one counting pass on 4096 depth buckets + in-bucket fix-up, radix for
+ * a list that puts more than 16 entries into one bucket.  Same sorted lists under every mode.  Returns the previous value. */
+int32_t gdr_set_tile_sort_mode(int32_t mode);
+/* Debug only: waits for the current device, then returns how many lists left the bucket path for the radix code since the
+ * counter was last cleared (reset != 0 clears it); < 0 on a HIP error.  Results never depend on the counter. */
+int64_t gdr_debug_tile_sort_fallbacks(int32_t reset);
 
 size_t gdr_geom_bytes(int32_t N);
 size_t gdr_binning_bytes(uint64_t D);
