@@ -183,6 +183,10 @@ GDR_NORM_DTYPES = {"f16": 0, "bf16": 1, "f32": 2}
 GDR_NORM_ROWS, GDR_NORM_MAX_CHANNELS, GDR_NORM_MAX_SEGMENTS, GDR_NORM_MAX_FREQS, GDR_NORM_MAX_UPSCALE = 32, 1024, 1024, 16, 16
 
 
+GDR_DENSIFY_MODES = {"top_k": 0, "top_p": 1}
+GDR_DENSIFY_MAX_SEGMENTS, GDR_DENSIFY_MAX_CHANNELS, GDR_DENSIFY_CHUNK = 1024, 1024, 1024
+
+
 class GdrSubmArgs(C.Structure):   # include/gdr.h gdr_subm_args
     _fields_ = [("N", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("K", C.c_int32), ("dtype", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -349,6 +353,19 @@ _PROTOS = {
     "gdr_norm_pe_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                        C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "gdr_densify_select_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gdr_densify_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_densify_gate_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_void_p]),
+    "gdr_densify_split_bytes": (C.c_size_t, [C.c_int64]),
+    "gdr_densify_split_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_densify_split_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                            C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
+    "gdr_densify_rows_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                            C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

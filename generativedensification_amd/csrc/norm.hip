@@ -35,7 +35,7 @@
 // outside the buffers.
 #include "gdr_common.h"
 #include "host_util.h"
-#include "half_bits.h"
+#include "row_io.h"
 
 namespace gdr {
 namespace {
@@ -47,35 +47,6 @@ constexpr int NM_FOLD_CH = NM_BLOCK / NM_FOLD_LANES;
 constexpr int NM_TRIG = 6 * GDR_NORM_MAX_FREQS;      // trig columns of a pe row at most
 constexpr int NM_PE_EXTRA = NM_TRIG + NM_TRIG / 2;   // LDS floats of a group in the pe backward beside the gradient row
 
-// ---- 8 / 2 / 1 elements of a runtime storage type <-> f32 -------------------------------------------------------------------
-__device__ __forceinline__ float up_any(uint16_t b, int dt) { return dt == GDR_NORM_BF16 ? up16<true>(b) : up16<false>(b); }
-__device__ __forceinline__ uint16_t down_any(float f, int dt) { return dt == GDR_NORM_BF16 ? down16<true>(f) : down16<false>(f); }
-
-// idx: an element index that is a multiple of 8 from a 16-byte aligned base
-__device__ __forceinline__ void load8(const void* base, int64_t idx, int dt, float (&x)[8]) {
-    if (dt == GDR_NORM_F32) {
-        const float4* p = reinterpret_cast<const float4*>((const float*)base + idx);
-        const float4 a = p[0], b = p[1];
-        x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-    } else {
-        union { uint4 raw; uint16_t e[8]; } u;
-        u.raw = *reinterpret_cast<const uint4*>((const uint16_t*)base + idx);
-#pragma unroll
-        for (int v = 0; v < 8; ++v) x[v] = up_any(u.e[v], dt);
-    }
-}
-__device__ __forceinline__ void store8(void* base, int64_t idx, int dt, const float (&x)[8]) {
-    if (dt == GDR_NORM_F32) {
-        float4* p = reinterpret_cast<float4*>((float*)base + idx);
-        p[0] = make_float4(x[0], x[1], x[2], x[3]);
-        p[1] = make_float4(x[4], x[5], x[6], x[7]);
-    } else {
-        union { uint4 raw; uint16_t e[8]; } u;
-#pragma unroll
-        for (int v = 0; v < 8; ++v) u.e[v] = down_any(x[v], dt);
-        *reinterpret_cast<uint4*>((uint16_t*)base + idx) = u.raw;
-    }
-}
 // idx: an even element index from a base aligned to two elements
 __device__ __forceinline__ void load2(const void* base, int64_t idx, int dt, float& a, float& b) {
     if (dt == GDR_NORM_F32) {
@@ -86,20 +57,6 @@ __device__ __forceinline__ void load2(const void* base, int64_t idx, int dt, flo
         a = up_any((uint16_t)(v & 0xffffu), dt); b = up_any((uint16_t)(v >> 16), dt);
     }
 }
-__device__ __forceinline__ float load1(const void* base, int64_t idx, int dt) {
-    return dt == GDR_NORM_F32 ? ((const float*)base)[idx] : up_any(((const uint16_t*)base)[idx], dt);
-}
-__device__ __forceinline__ void store1(void* base, int64_t idx, int dt, float x) {
-    if (dt == GDR_NORM_F32) ((float*)base)[idx] = x;
-    else ((uint16_t*)base)[idx] = down_any(x, dt);
-}
-
-// the sum over the LC lanes of a group, the same bits in every lane (lc = LC)
-__device__ __forceinline__ float group_sum(float v, int lc) {
-    for (int m = lc >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, GDR_WAVE);
-    return v;
-}
-
 __device__ __forceinline__ int64_t clamp_end(const int64_t* __restrict__ offset, int i, int64_t N) {
     const int64_t v = offset[i];
     return v < 0 ? 0 : (v > N ? N : v);
@@ -528,15 +485,6 @@ int check_pe(int64_t P, int64_t S, int64_t C, int64_t F) {
     if (S < 1 || S > GDR_NORM_MAX_UPSCALE) return unsupported("norm_pe: S must be in 1..GDR_NORM_MAX_UPSCALE");
     if (P > NM_MAX_ROWS / S) return unsupported("norm_pe: P * S must be below 2^31");
     return check_channels(C);
-}
-
-// lanes per row (as a shift, 8..64 lanes) and 8-channel pieces per lane
-void row_shape(int C, int32_t* lc_shift, int* K) {
-    const int vecs = C / 8;
-    int sh = 3;
-    while (sh < 6 && (1 << sh) < vecs) ++sh;
-    *lc_shift = sh;
-    *K = vecs > (1 << sh) ? 2 : 1;
 }
 
 // a (rows, C) matrix read or written in 8-element pieces: 16-byte base, a stride that is a multiple of 8 and at least C

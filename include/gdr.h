@@ -875,6 +875,55 @@ int gdr_norm_pe_backward(const void* grad_out, int64_t grad_stride, int32_t grad
                          const void* feat, int64_t feat_stride, int32_t feat_dtype, const void* freq, int32_t freq_dtype, int64_t P,
                          int32_t S, int32_t C, int32_t F, float eps, void* grad_x, void* grad_feat, void* stream);
 
+/* ---- densification masks of the point decoder (csrc/densify.hip; added in v17, backward-compatible) ------------------------
+ * What the reference's MaskModule / MaskResModule do around their scores: per-segment top-k / top-p selection, the
+ * straight-through gate and the split into selected and remaining rows.  The rules are restated in the header of
+ * csrc/densify.hip.  The caller owns every buffer; all are device memory.  Every `*_dtype` is one of GDR_NORM_F16 / BF16 / F32.
+ * Refusals happen before any launch; no entry point allocates or synchronises with the host.  No atomics: two runs are
+ * bitwise equal.  Envelope (GDR_ERR_UNSUPPORTED beyond it): N <= 2^30, 1 <= B <= GDR_DENSIFY_MAX_SEGMENTS, C a multiple of 8
+ * in 8..GDR_DENSIFY_MAX_CHANNELS.  "rows of X" means a 16-byte aligned base and a row stride (elements) that is a multiple of
+ * 8 and >= C.
+ *
+ * select: x: N dense values of x_dtype; offset: B int64 segment ends, clamped on the device to [previous end, N]; mask: N
+ *   bytes (0 / 1), written whole; new_offset: B int64.  Rows of a segment are ranked by descending value (NaN first, -0 = +0,
+ *   ties by ascending row).  GDR_DENSIFY_TOP_K selects the first min(k_b, n_b) ranks, k_b = ceil(ratio * n_b) with both the
+ *   count and the product rounded to x_dtype; GDR_DENSIFY_TOP_P selects rank j iff the inclusive f32 prefix sum of the ranked
+ *   values, rounded to x_dtype, is <= threshold (the caller's ratio rounded to x_dtype).  Rows at or behind the last end are
+ *   never selected.  workspace: gdr_densify_select_bytes(N, B) bytes, 256-byte aligned.  3 (top-k) or 8 (top-p) launches +
+ *   gdr_serial_sort on 32 / 19 / 16 (f32 / f16 / bf16) + bits(B) key bits.
+ * gate_forward: rows of feat (N, C); mask NULL or N bytes; out (N, C) dense of out_dtype = feat, or zero where mask is 0.
+ * split_scan: dest[i] = the number of rows before i with the same mask value, *count = the number of selected rows.
+ *   workspace: gdr_densify_split_bytes(N) bytes, 256-byte aligned.  3 launches.
+ * split_forward: row i of feat (converted to out_dtype) and of coord (N, coord_elems) dense elements of coord_elem_bytes (1,
+ *   2, 4 or 8) goes to row dest[i] of feat_sel / coord_sel (mask 1) or feat_rest / coord_rest (mask 0), all dense.  A row
+ *   whose destination is not below n_sel / n_rest, the capacities of the outputs in rows, is dropped.  1 launch.
+ * rows_backward: the backward of the gate (dest NULL: the gradient row of row i is row i of grad_sel through grad_stride) and
+ *   of the split (row dest[i] of grad_sel / grad_rest, rows of (n, C) of grad_dtype; zero for a dropped row).  grad_feat (N, C)
+ *   dense of feat_dtype = prob[i] * g (g if prob is NULL); grad_prob: N of prob_dtype = sum_c feat[i, c] * g[c] in f32;
+ *   grad_coord (N, coord_elems) = the coord gradient row.  A NULL output is not wanted.  1 launch. */
+#define GDR_DENSIFY_TOP_K 0
+#define GDR_DENSIFY_TOP_P 1
+#define GDR_DENSIFY_MAX_SEGMENTS 1024
+#define GDR_DENSIFY_MAX_CHANNELS 1024
+#define GDR_DENSIFY_CHUNK 1024         /* rows per workgroup of the scans */
+size_t gdr_densify_select_bytes(int64_t N, int32_t B);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_densify_select(const void* x, int32_t x_dtype, const int64_t* offset, int64_t N, int32_t B, int32_t mode, float ratio,
+                       float threshold, void* workspace, size_t workspace_bytes, uint8_t* mask, int64_t* new_offset, void* stream);
+int gdr_densify_gate_forward(const void* feat, int64_t feat_stride, int32_t feat_dtype, const uint8_t* mask, int64_t N, int32_t C,
+                             void* out, int32_t out_dtype, void* stream);
+size_t gdr_densify_split_bytes(int64_t N);               /* 0: the arguments are refused (gdr_last_error) */
+int gdr_densify_split_scan(const uint8_t* mask, int64_t N, void* workspace, size_t workspace_bytes, int64_t* dest, int64_t* count,
+                           void* stream);
+int gdr_densify_split_forward(const uint8_t* mask, const int64_t* dest, int64_t N, int32_t C, const void* feat, int64_t feat_stride,
+                              int32_t feat_dtype, const void* coord, int32_t coord_elems, int32_t coord_elem_bytes, int64_t n_sel,
+                              int64_t n_rest, void* feat_sel, void* feat_rest, int32_t out_dtype, void* coord_sel, void* coord_rest,
+                              void* stream);
+int gdr_densify_rows_backward(const uint8_t* mask, const int64_t* dest, int64_t N, int32_t C, const void* grad_sel, const void* grad_rest,
+                              int64_t grad_stride, int32_t grad_dtype, int64_t n_sel, int64_t n_rest, const void* feat,
+                              int64_t feat_stride, int32_t feat_dtype, const void* prob, int32_t prob_dtype, const void* gcoord_sel,
+                              const void* gcoord_rest, int32_t coord_elems, int32_t coord_elem_bytes, void* grad_feat, void* grad_prob,
+                              void* grad_coord, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
