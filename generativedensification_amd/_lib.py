@@ -366,6 +366,10 @@ _PROTOS = {
     "gdr_densify_rows_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                             C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_viewattn_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 2 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                       C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "gdr_viewattn_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

@@ -924,6 +924,28 @@ int gdr_densify_rows_backward(const uint8_t* mask, const int64_t* dest, int64_t 
                               const void* gcoord_rest, int32_t coord_elems, int32_t coord_elem_bytes, void* grad_feat, void* grad_prob,
                               void* grad_coord, void* stream);
 
+/* ---- per-point view cross attention, folded form (csrc/viewattn.hip; added in v17, backward-compatible) ---------------------
+ * The core of a single-query multi-head cross attention over the V views of a point, with the key / value projections folded
+ * into the query and the output (generativedensification_amd/viewattn.py): s[n, h, v] = scale * <t[n, h], cond[n, v]>,
+ * p = softmax_v(s), u[n, h] = sum_v p[n, h, v] * cond[n, v].  The arithmetic and its backward are restated in the header of
+ * csrc/viewattn.hip.  The caller owns every buffer; all are device memory.  Every `*_dtype` is one of GDR_NORM_F16 / BF16 / F32
+ * and the types of one call are independent; the arithmetic is f32.  Refusals happen before any launch; N = 0 returns GDR_OK
+ * without one; no entry point allocates or synchronises with the host; no workspace.  No atomics: two runs are bitwise equal.
+ * Envelope (GDR_ERR_UNSUPPORTED beyond it): Ck 4, 8 or 16, 1 <= H <= GDR_VIEWATTN_MAX_HEADS, 1 <= V <= GDR_VIEWATTN_MAX_VIEWS,
+ * N <= 2^27, and "rows of X": a 16-byte aligned base and a row stride (in elements) that is a multiple of 8 and >= the row.
+ *
+ * forward: rows of t (N, H * Ck), cond (N, V * Ck) and out (N, H * Ck, written through out_stride).  1 launch.
+ * backward: rows of grad_out (N, H * Ck), t and cond as in the forward; p is recomputed.  grad_t (N, H * Ck) dense of t_dtype and
+ *   grad_cond (N, V * Ck) dense of cond_dtype, both 16-byte aligned and written whole.  1 launch. */
+#define GDR_VIEWATTN_MAX_HEADS 64
+#define GDR_VIEWATTN_MAX_VIEWS 16
+int gdr_viewattn_forward(const void* t, int64_t t_stride, int32_t t_dtype, const void* cond, int64_t cond_stride, int32_t cond_dtype,
+                         int64_t N, int32_t H, int32_t Ck, int32_t V, float scale, void* out, int64_t out_stride, int32_t out_dtype,
+                         void* stream);
+int gdr_viewattn_backward(const void* grad_out, int64_t grad_out_stride, int32_t grad_out_dtype, const void* t, int64_t t_stride,
+                          int32_t t_dtype, const void* cond, int64_t cond_stride, int32_t cond_dtype, int64_t N, int32_t H, int32_t Ck,
+                          int32_t V, float scale, void* grad_t, void* grad_cond, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
