@@ -1,6 +1,14 @@
 // device_math.h — per-Gaussian device helpers shared by preprocess.hip (3DGS path) and preprocess_surfel.hip
 // (2DGS path): camera block, SH basis + gradient (expression trees identical to the oracle's), quaternion ->
-// rotation, and the adaptor activations that can be folded into K1/K9.  Include inside a translation unit
+// rotation, the adaptor activations that can be folded into K1/K9 with their derivatives, and the per-Gaussian
+// arithmetic that K1 / K9 of both paths have in common (to_view, view_dir, sh_colour, sh_backward, tile_rect,
+// quat_grad, the tile sums).  Every single-view and multi-view kernel calls these, and the path-specific helpers at
+// the top of preprocess.hip (cov3d_of, project, cov2d_det, splat_radius, ndc2pix, conic_of, conic_grad_of, cov2d_grad,
+// the record stores) and of preprocess_surfel.hip (surfel_normal, surfel_aabb, write_surfel_rec): an expression tree
+// with ONE definition is what keeps single-view and multi-view results equal bit for bit.  (The multi-view 3DGS K9 and
+// the surfel K9s kernels still write out part of their per-view chain; the comments above them say which part and why.
+// Prefer helpers that return a scalar or a float3 / float4 and are called where the lines stood: those compile to the
+// written-out code, helpers handing back structs or arrays have not.)  Include inside a translation unit
 // compiled with -ffp-contract=off when integer intermediates must match the oracle bit for bit.
 #pragma once
 #include "gdr_common.h"
@@ -116,6 +124,121 @@ __device__ __forceinline__ float4 act_normalize(float4 q, float* inv_norm) {
     const float inv = 1.f / fmaxf(n, 1e-12f);  // F.normalize(eps=1e-12)
     *inv_norm = inv;
     return make_float4(q.x * inv, q.y * inv, q.z * inv, q.w * inv);
+}
+// their derivatives: d exp(x) = exp(x) = s, and d (q / |q|) = (I - q^ q^T) / |q| for the normalised q^ and inv_n = 1 / |q|
+__device__ __forceinline__ float act_exp_grad(float d, float s) { return d * s; }
+__device__ __forceinline__ float4 act_normalize_grad(float4 q, float4 d, float inv_n) {
+    const float dot = (q.x * d.x + q.y * d.y) + (q.z * d.z + q.w * d.w);
+    return make_float4((d.x - q.x * dot) * inv_n, (d.y - q.y * dot) * inv_n, (d.z - q.z * dot) * inv_n,
+                       (d.w - q.w * dot) * inv_n);
+}
+
+// ---- per-Gaussian arithmetic of K1 / K9, defined ONCE for the single-view and the multi-view kernels of both paths ----
+// Values in, values out: the kernels keep their loads and stores, and where one kernel assigns a term that another
+// accumulates, the helper returns the term and the caller assigns or adds it (x = t and x += t differ in the sign of a
+// zero, and a pre-summed pair of terms rounds differently from two additions onto a running sum).
+
+// world -> view space of a mean
+__device__ __forceinline__ float3 to_view(const Cam& cam, float x, float y, float z) {
+    return make_float3(cam.v[0] * x + cam.v[4] * y + cam.v[8] * z + cam.v[12],
+                       cam.v[1] * x + cam.v[5] * y + cam.v[9] * z + cam.v[13],
+                       cam.v[2] * x + cam.v[6] * y + cam.v[10] * z + cam.v[14]);
+}
+
+// unit vector from the camera to a mean; returns 1 / distance
+__device__ __forceinline__ float view_dir(const Cam& cam, float x, float y, float z, float (&u)[3]) {
+    const float dx = x - cam.c[0], dy = y - cam.c[1], dz = z - cam.c[2];
+    const float inv = 1.f / sqrtf((dx * dx + dy * dy) + dz * dz);
+    u[0] = dx * inv; u[1] = dy * inv; u[2] = dz * inv;
+    return inv;
+}
+
+// SH row -> clamped colour in direction u; returns the clamp bits (bit ch: channel ch was negative)
+template <int DEG>
+__device__ __forceinline__ uint32_t sh_colour(const float (&u)[3], const float (&sh)[3 * (DEG + 1) * (DEG + 1)],
+                                              float (&rgb)[3]) {
+    constexpr int NB = (DEG + 1) * (DEG + 1);
+    float bk[NB];
+    sh_basis<DEG>(u[0], u[1], u[2], bk);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) rgb[ch] = bk[0] * sh[ch];
+#pragma unroll
+    for (int k = 1; k < NB; ++k)
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) rgb[ch] = rgb[ch] + bk[k] * sh[3 * k + ch];
+    uint32_t clampbits = 0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        rgb[ch] = rgb[ch] + 0.5f;
+        if (rgb[ch] < 0.f) clampbits |= (1u << ch);
+        rgb[ch] = fmaxf(rgb[ch], 0.f);
+    }
+    return clampbits;
+}
+
+// SH backward of one view (A.5-iv): basis bk and clamp-masked colour gradient g (dL/dsh[k][ch] = bk[k] g[ch], which the
+// caller stores or sums), and the terms dm that the direction's dependence on the mean adds to dL/dmean
+template <int DEG>
+__device__ __forceinline__ void sh_backward(const float (&u)[3], float inv, const float (&sh)[3 * (DEG + 1) * (DEG + 1)],
+                                            float gr, float gg, float gb, uint32_t cl,
+                                            float (&bk)[(DEG + 1) * (DEG + 1)], float (&g)[3], float (&dm)[3]) {
+    constexpr int NB = (DEG + 1) * (DEG + 1);
+    float bx[NB], by[NB], bz[NB];
+    sh_basis<DEG>(u[0], u[1], u[2], bk);
+    sh_basis_grad<DEG>(u[0], u[1], u[2], bx, by, bz);
+    g[0] = (cl & 1u) ? 0.f : gr; g[1] = (cl & 2u) ? 0.f : gg; g[2] = (cl & 4u) ? 0.f : gb;
+    float ddx = 0.f, ddy = 0.f, ddz = 0.f;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float sg = sh[3 * k + ch] * g[ch];
+            ddx += bx[k] * sg;
+            ddy += by[k] * sg;
+            ddz += bz[k] * sg;
+        }
+    }
+    const float dot = u[0] * ddx + u[1] * ddy + u[2] * ddz;
+    dm[0] = (ddx - u[0] * dot) * inv;
+    dm[1] = (ddy - u[1] * dot) * inv;
+    dm[2] = (ddz - u[2] * dot) * inv;
+}
+
+// tile rectangle [x, z) x [y, w) covered by the square of half-side r around (cx, cy); returns the number of tiles
+__device__ __forceinline__ uint32_t tile_rect(float cx, float cy, int r, int gx, int gy, int4& rect) {
+    const float rf = (float)r;
+    rect.x = min(gx, max(0, (int)((cx - rf) / (float)GDR_TILE)));
+    rect.y = min(gy, max(0, (int)((cy - rf) / (float)GDR_TILE)));
+    rect.z = min(gx, max(0, (int)((cx + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
+    rect.w = min(gy, max(0, (int)((cy + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
+    return (uint32_t)((rect.z - rect.x) * (rect.w - rect.y));
+}
+
+// dL/dq (r, x, y, z) from dL/dR of quat_to_R
+__device__ __forceinline__ float4 quat_grad(float4 q, const float (&dR)[9]) {
+    const float qr = q.x, qx = q.y, qy = q.z, qz = q.w;
+#define G_(r_, c_) dR[3 * (r_) + (c_)]
+    float4 d;
+    d.x = 2.f * (-qz * G_(0, 1) + qy * G_(0, 2) + qz * G_(1, 0) - qx * G_(1, 2) - qy * G_(2, 0) + qx * G_(2, 1));
+    d.y = 2.f * (qy * G_(0, 1) + qz * G_(0, 2) + qy * G_(1, 0) - 2.f * qx * G_(1, 1) - qr * G_(1, 2) + qz * G_(2, 0) + qr * G_(2, 1) - 2.f * qx * G_(2, 2));
+    d.z = 2.f * (-2.f * qy * G_(0, 0) + qx * G_(0, 1) + qr * G_(0, 2) + qx * G_(1, 0) + qz * G_(1, 2) - qr * G_(2, 0) + qz * G_(2, 1) - 2.f * qy * G_(2, 2));
+    d.w = 2.f * (-2.f * qz * G_(0, 0) - qr * G_(0, 1) + qx * G_(0, 2) + qr * G_(1, 0) - 2.f * qz * G_(1, 1) + qy * G_(1, 2) + qx * G_(2, 0) + qy * G_(2, 1));
+#undef G_
+    return d;
+}
+
+// tiles_touched of a view: wave sum -> wsum[wave]; after a __syncthreads() ONE thread publishes the block's sum (which
+// feeds the scan, K2) and takes the block's slice of the view's duplicate list
+__device__ __forceinline__ void wave_tiles_sum(uint32_t tiles, uint32_t (&wsum)[GDR_BLOCK / GDR_WAVE]) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tiles += __shfl_xor(tiles, off, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = tiles;
+}
+__device__ __forceinline__ void publish_block_sum(const uint32_t (&wsum)[GDR_BLOCK / GDR_WAVE],
+                                                  uint32_t* block_sums, uint32_t* block_offs, uint32_t* num_rendered) {
+    const uint32_t bs = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    block_sums[blockIdx.x] = bs;
+    block_offs[blockIdx.x] = bs ? atomicAdd(num_rendered, bs) : 0u;
 }
 
 

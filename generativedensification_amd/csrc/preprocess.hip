@@ -79,6 +79,180 @@ __device__ __forceinline__ void ewa(const Cam& cam, float pvx, float pvy, float 
     e.c = ((e.A1[0] * e.v1[0] + e.A1[1] * e.v1[1]) + e.A1[2] * e.v1[2]) + 0.3f;
 }
 
+// The rest of the 3DGS per-Gaussian arithmetic, each expression tree defined once for the single-view and the multi-view
+// kernels (what the surfel path shares as well is in device_math.h).
+
+// cov3D (upper triangle) = (R S)(R S)^T from the activated quaternion and scales
+__device__ __forceinline__ void cov3d_of(float4 q, float sc0, float sc1, float sc2, float scale_modifier, float (&c6)[6]) {
+    float R[9], Mm[9];
+    quat_to_R(q.x, q.y, q.z, q.w, R);
+    const float s[3] = {scale_modifier * sc0, scale_modifier * sc1, scale_modifier * sc2};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Mm[r * 3 + k] = R[r * 3 + k] * s[k];
+#define SIG(a_, b_) ((Mm[a_ * 3 + 0] * Mm[b_ * 3 + 0] + Mm[a_ * 3 + 1] * Mm[b_ * 3 + 1]) + Mm[a_ * 3 + 2] * Mm[b_ * 3 + 2])
+    c6[0] = SIG(0, 0); c6[1] = SIG(0, 1); c6[2] = SIG(0, 2);
+    c6[3] = SIG(1, 1); c6[4] = SIG(1, 2); c6[5] = SIG(2, 2);
+#undef SIG
+}
+
+// homogeneous projection of a mean: clip x, clip y and 1 / (clip w + 1e-7)
+__device__ __forceinline__ float3 project(const Cam& cam, float x, float y, float z) {
+    const float hx = cam.p[0] * x + cam.p[4] * y + cam.p[8] * z + cam.p[12];
+    const float hy = cam.p[1] * x + cam.p[5] * y + cam.p[9] * z + cam.p[13];
+    const float hw = cam.p[3] * x + cam.p[7] * y + cam.p[11] * z + cam.p[15];
+    return make_float3(hx, hy, 1.0f / (hw + 0.0000001f));
+}
+
+// integer radius of the 3-sigma circle around a 2D covariance (a b; b c) of determinant det (A.1-4)
+__device__ __forceinline__ int splat_radius(float a, float c, float det) {
+    const float mid = 0.5f * (a + c);
+    const float disc = sqrtf(fmaxf(0.1f, mid * mid - det));
+    const float lambda1 = mid + disc, lambda2 = mid - disc;
+    const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
+    return (int)my_radius;
+}
+// NDC coordinate -> pixel coordinate on an axis of S pixels
+__device__ __forceinline__ float ndc2pix(float v, int S) { return ((v + 1.0f) * (float)S - 1.0f) * 0.5f; }
+
+// determinant of the 2D covariance, and its inverse matrix (the conic) from 1 / determinant
+__device__ __forceinline__ float cov2d_det(const Ewa& e) { return e.a * e.c - e.b * e.b; }
+__device__ __forceinline__ float3 conic_of(const Ewa& e, float det_inv) {
+    return make_float3(e.c * det_inv, -e.b * det_inv, e.a * det_inv);
+}
+// K1 strings these together itself (project, ewa, cov2d_det, splat_radius, ndc2pix, tile_rect, conic_of), in the same
+// order in the single-view and the multi-view kernel.  One helper that returned the whole splat in a struct cost the
+// multi-view kernels 2 to 7 VGPRs and about 1 % of their time at degree 3; these scalar pieces compile to the code the
+// written-out block did.
+
+// dL/dconic as K7 leaves it -> true partials (the exact factors -1/2, -1, -1/2 are K9's to apply); .w (dL/ddepth) as is
+__device__ __forceinline__ float4 conic_grad_of(float4 g) { return make_float4(g.x * -0.5f, -g.y, g.z * -0.5f, g.w); }
+// dL/dconic -> dL/d(a, b, c) of the 2D covariance of determinant det != 0
+__device__ __forceinline__ float3 cov2d_grad(float a, float b, float c, float det, float4 gconic) {
+    const float d2 = 1.f / (det * det);
+    return make_float3(d2 * (-c * c * gconic.x + b * c * gconic.y - b * b * gconic.z),
+                       d2 * (2.f * b * c * gconic.x - (a * c + b * b) * gconic.y + 2.f * a * b * gconic.z),
+                       d2 * (-b * b * gconic.x + a * b * gconic.y - a * a * gconic.z));
+}
+
+// One view's chain from the gradient record back to the covariance and the mean (A.5-i..iii).  g2: dL/dmean2D;
+// gconic: dL/dconic as K7 leaves it (the exact factors -1/2, -1, -1/2 are applied here).
+// has_cov is false where the 2D covariance is singular: dcov is then NOT a term (the caller leaves its own untouched).
+// The mean gets two terms from here, through the EWA Jacobian and through the projected centre, which the caller assigns
+// or adds ONE AFTER THE OTHER; the depth term (risk R1 switch GDR_IN_NO_DEPTH_TO_MEAN) is the caller's.
+struct ConicGrad {
+    bool has_cov;
+    float dcov[6];
+    float dmean_ewa[3], dmean_proj[3];
+};
+__device__ __forceinline__ void conic_backward(const Cam& cam, float x, float y, float z, const float (&c6)[6],
+                                               float focal_x, float focal_y, float tanx, float tany, float4 g2,
+                                               float4 gconic, ConicGrad& o) {
+    gconic = conic_grad_of(gconic);
+    const float3 pv = to_view(cam, x, y, z);
+    Ewa e;
+    ewa(cam, pv.x, pv.y, pv.z, c6, focal_x, focal_y, tanx, tany, e);
+    const float det = cov2d_det(e);
+    float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
+    o.has_cov = det * det != 0.f;
+    if (o.has_cov) {
+        const float3 d = cov2d_grad(e.a, e.b, e.c, det, gconic);
+        dL_da = d.x; dL_db = d.y; dL_dc = d.z;
+        const float* A0 = e.A0;
+        const float* A1 = e.A1;
+        o.dcov[0] = A0[0] * A0[0] * dL_da + A0[0] * A1[0] * dL_db + A1[0] * A1[0] * dL_dc;
+        o.dcov[3] = A0[1] * A0[1] * dL_da + A0[1] * A1[1] * dL_db + A1[1] * A1[1] * dL_dc;
+        o.dcov[5] = A0[2] * A0[2] * dL_da + A0[2] * A1[2] * dL_db + A1[2] * A1[2] * dL_dc;
+        o.dcov[1] = 2.f * A0[0] * A0[1] * dL_da + (A0[0] * A1[1] + A0[1] * A1[0]) * dL_db + 2.f * A1[0] * A1[1] * dL_dc;
+        o.dcov[2] = 2.f * A0[0] * A0[2] * dL_da + (A0[0] * A1[2] + A0[2] * A1[0]) * dL_db + 2.f * A1[0] * A1[2] * dL_dc;
+        o.dcov[4] = 2.f * A0[1] * A0[2] * dL_da + (A0[1] * A1[2] + A0[2] * A1[1]) * dL_db + 2.f * A1[1] * A1[2] * dL_dc;
+    }
+    float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float dA0 = 2.f * dL_da * e.v0[k] + dL_db * e.v1[k];
+        const float dA1 = 2.f * dL_dc * e.v1[k] + dL_db * e.v0[k];
+        dJ00 += dA0 * cam.v[4 * k + 0];
+        dJ02 += dA0 * cam.v[4 * k + 2];
+        dJ11 += dA1 * cam.v[4 * k + 1];
+        dJ12 += dA1 * cam.v[4 * k + 2];
+    }
+    const float tz1 = 1.f / e.tz, tz2 = tz1 * tz1, tz3 = tz2 * tz1;
+    const float dtx = e.xmul * (-focal_x * tz2 * dJ02);
+    const float dty = e.ymul * (-focal_y * tz2 * dJ12);
+    const float dtz = -focal_x * tz2 * dJ00 - focal_y * tz2 * dJ11 +
+                      (2.f * focal_x * e.tx) * tz3 * dJ02 + (2.f * focal_y * e.ty) * tz3 * dJ12;
+    const float3 mh = project(cam, x, y, z);
+    const float m_w = mh.z;
+    const float mul1 = mh.x * m_w * m_w, mul2 = mh.y * m_w * m_w;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o.dmean_ewa[k] = cam.v[4 * k + 0] * dtx + cam.v[4 * k + 1] * dty + cam.v[4 * k + 2] * dtz;
+        o.dmean_proj[k] = (cam.p[4 * k + 0] * m_w - cam.p[4 * k + 3] * mul1) * g2.x +
+                          (cam.p[4 * k + 1] * m_w - cam.p[4 * k + 3] * mul2) * g2.y;
+    }
+}
+
+// dL/dcov3D -> dL/dscale, dL/dquaternion (A.5-v), through the folded activations where flags has them (sc*: the
+// activated scales, q: the normalised quaternion with inv_n = 1 / |raw q|)
+__device__ __forceinline__ void cov3d_backward(float4 q, float inv_n, float sc0, float sc1, float sc2, float scale_modifier,
+                                               const float (&dcov)[6], uint32_t flags, float (&dscale)[3], float4& drot) {
+    float R[9];
+    quat_to_R(q.x, q.y, q.z, q.w, R);
+    const float s[3] = {scale_modifier * sc0, scale_modifier * sc1, scale_modifier * sc2};
+    const float Gs[9] = {dcov[0], 0.5f * dcov[1], 0.5f * dcov[2], 0.5f * dcov[1], dcov[3],
+                         0.5f * dcov[4], 0.5f * dcov[2], 0.5f * dcov[4], dcov[5]};
+    float dR[9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float ds = 0.f;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            float acc = 0.f;
+#pragma unroll
+            for (int l = 0; l < 3; ++l) acc += Gs[3 * r + l] * (R[3 * l + k] * s[k]);
+            const float dM = 2.f * acc;
+            ds += R[3 * r + k] * dM;
+            dR[3 * r + k] = s[k] * dM;
+        }
+        dscale[k] = scale_modifier * ds;
+    }
+    drot = quat_grad(q, dR);
+    if (flags & GDR_IN_RAW_SCALES) {
+        dscale[0] = act_exp_grad(dscale[0], sc0); dscale[1] = act_exp_grad(dscale[1], sc1); dscale[2] = act_exp_grad(dscale[2], sc2);
+    }
+    if (flags & GDR_IN_RAW_ROTATIONS) drot = act_normalize_grad(q, drot, inv_n);
+}
+
+// A lane's render record into its slot of the workgroup's OUT slice (REC_STRIDE floats per slot: (stride / 4) odd, so
+// the 16-byte accesses of consecutive lanes rotate through the banks) ...
+constexpr int REC_STRIDE = 20;
+__device__ __forceinline__ void stage_rec(float* rec_out, float2 pxy, float depth, float4 con_o, float4 rgbd) {
+    const float2 ext = alpha_extent(con_o);
+    float* mine = rec_out + (int)threadIdx.x * REC_STRIDE;
+    *reinterpret_cast<float4*>(mine) = make_float4(pxy.x, pxy.y, depth, 0.f);
+    *reinterpret_cast<float4*>(mine + 4) = con_o;
+    *reinterpret_cast<float4*>(mine + 8) = rgbd;
+    *reinterpret_cast<float4*>(mine + 12) = make_float4(ext.x, ext.y, 0.f, 0.f);
+}
+// ... and the wave's 64 records (4 KB contiguous in the view's record array) out of it: four coalesced 1 KB stores per
+// wave instead of 64-line-stride float4 stores per lane.  Every lane of the wave calls it, past the end of the rows too.
+__device__ __forceinline__ void store_wave_recs(const float* rec_out, float4* g_rec, int N) {
+    const int wave0 = (int)(threadIdx.x & ~63u), lane = (int)(threadIdx.x & 63u);
+    const int first = blockIdx.x * GDR_BLOCK + wave0;          // first Gaussian of this wave
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const int nrec = min(GDR_WAVE, N - first);                   // (<= 0 for a wave past the end)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int q = lane + GDR_WAVE * j;                       // float4 index inside the wave's 4 KB span
+        const int r = q >> 2, c = q & 3;
+        if (r < nrec) g_rec[4 * (size_t)first + q] = *reinterpret_cast<const float4*>(rec_out + (wave0 + r) * REC_STRIDE + 4 * c);
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // K1
 // ---------------------------------------------------------------------------------
@@ -98,7 +272,6 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_kernel(
     load_cam(cam, view, proj, campos);
     const int i = blockIdx.x * GDR_BLOCK + threadIdx.x;
     const int gx = (W + GDR_TILE - 1) / GDR_TILE, gy = (H + GDR_TILE - 1) / GDR_TILE;
-    constexpr int REC_STRIDE = 20;
     __shared__ float rec_out[GDR_BLOCK * REC_STRIDE];
 
     uint32_t tiles = 0;
@@ -113,9 +286,7 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_kernel(
         float c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
         const float px_ = means3D[3 * i], py_ = means3D[3 * i + 1], pz_ = means3D[3 * i + 2];
-        const float pvx = cam.v[0] * px_ + cam.v[4] * py_ + cam.v[8] * pz_ + cam.v[12];
-        const float pvy = cam.v[1] * px_ + cam.v[5] * py_ + cam.v[9] * pz_ + cam.v[13];
-        const float pvz = cam.v[2] * px_ + cam.v[6] * py_ + cam.v[10] * pz_ + cam.v[14];
+        const float3 pv = to_view(cam, px_, py_, pz_);
         // cov3D of EVERY Gaussian, also of those this view culls: a render group's multi-view K8+K9 reads ONE view's copy
         // for all its views, and a Gaussian behind this camera's near plane may be visible to the next one
         if (cov3D_precomp) {
@@ -126,78 +297,43 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_kernel(
             float sc0 = scales[3 * i], sc1 = scales[3 * i + 1], sc2 = scales[3 * i + 2];
             if (flags & GDR_IN_RAW_ROTATIONS) { float inv_n; q = act_normalize(q, &inv_n); }
             if (flags & GDR_IN_RAW_SCALES) { sc0 = expf(sc0); sc1 = expf(sc1); sc2 = expf(sc2); }
-            float R[9], Mm[9];
-            quat_to_R(q.x, q.y, q.z, q.w, R);
-            const float s[3] = {scale_modifier * sc0, scale_modifier * sc1, scale_modifier * sc2};
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) Mm[r * 3 + k] = R[r * 3 + k] * s[k];
-#define SIG(a_, b_) ((Mm[a_ * 3 + 0] * Mm[b_ * 3 + 0] + Mm[a_ * 3 + 1] * Mm[b_ * 3 + 1]) + Mm[a_ * 3 + 2] * Mm[b_ * 3 + 2])
-            c6[0] = SIG(0, 0); c6[1] = SIG(0, 1); c6[2] = SIG(0, 2);
-            c6[3] = SIG(1, 1); c6[4] = SIG(1, 2); c6[5] = SIG(2, 2);
-#undef SIG
+            cov3d_of(q, sc0, sc1, sc2, scale_modifier, c6);
         }
-        bool ok = pvz > 0.2f;  // near cull (A.1-1); no x/y frustum test when prefiltered=False
+        bool ok = pv.z > 0.2f;  // near cull (A.1-1); no x/y frustum test when prefiltered=False
         if (ok) {
-            const float phx = cam.p[0] * px_ + cam.p[4] * py_ + cam.p[8] * pz_ + cam.p[12];
-            const float phy = cam.p[1] * px_ + cam.p[5] * py_ + cam.p[9] * pz_ + cam.p[13];
-            const float phw = cam.p[3] * px_ + cam.p[7] * py_ + cam.p[11] * pz_ + cam.p[15];
-            const float p_w = 1.0f / (phw + 0.0000001f);
-            const float ppx = phx * p_w, ppy = phy * p_w;
+            const float3 ph = project(cam, px_, py_, pz_);
+            const float ppx = ph.x * ph.z, ppy = ph.y * ph.z;
 
             Ewa e;
-            ewa(cam, pvx, pvy, pvz, c6, focal_x, focal_y, tanx, tany, e);
-            const float det = e.a * e.c - e.b * e.b;
+            ewa(cam, pv.x, pv.y, pv.z, c6, focal_x, focal_y, tanx, tany, e);
+            const float det = cov2d_det(e);
             ok = det != 0.f;
             if (ok) {
                 const float det_inv = 1.f / det;
-                const float mid = 0.5f * (e.a + e.c);
-                const float disc = sqrtf(fmaxf(0.1f, mid * mid - det));
-                const float lambda1 = mid + disc, lambda2 = mid - disc;
-                const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
-                const float sx = ((ppx + 1.0f) * (float)W - 1.0f) * 0.5f;
-                const float sy = ((ppy + 1.0f) * (float)H - 1.0f) * 0.5f;
-                const int r_i = (int)my_radius;
-                const float rf = (float)r_i;
-                rect.x = min(gx, max(0, (int)((sx - rf) / (float)GDR_TILE)));
-                rect.y = min(gy, max(0, (int)((sy - rf) / (float)GDR_TILE)));
-                rect.z = min(gx, max(0, (int)((sx + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
-                rect.w = min(gy, max(0, (int)((sy + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
-                tiles = (uint32_t)((rect.z - rect.x) * (rect.w - rect.y));
+                const int r_i = splat_radius(e.a, e.c, det);
+                const float sx = ndc2pix(ppx, W), sy = ndc2pix(ppy, H);
+                tiles = tile_rect(sx, sy, r_i, gx, gy, rect);
                 ok = tiles != 0;
                 if (ok) {
                     rad = r_i;
-                    depth = pvz;
+                    depth = pv.z;
                     pxy = make_float2(sx, sy);
                     const float op = (flags & GDR_IN_RAW_OPACITY) ? act_sigmoid(opacities[i]) : opacities[i];
-                    con_o = make_float4(e.c * det_inv, -e.b * det_inv, e.a * det_inv, op);
+                    const float3 conic = conic_of(e, det_inv);
+                    con_o = make_float4(conic.x, conic.y, conic.z, op);
                     if (colors_precomp) {
                         rgbd.x = colors_precomp[3 * i];
                         rgbd.y = colors_precomp[3 * i + 1];
                         rgbd.z = colors_precomp[3 * i + 2];
                     } else {
-                        float dx = px_ - cam.c[0], dy = py_ - cam.c[1], dz = pz_ - cam.c[2];
-                        const float inv = 1.f / sqrtf((dx * dx + dy * dy) + dz * dz);
-                        dx *= inv; dy *= inv; dz *= inv;
                         constexpr int NB = (DEG + 1) * (DEG + 1);
-                        float bk[NB];
-                        sh_basis<DEG>(dx, dy, dz, bk);
-                        const float* sh = shs + (size_t)i * M * 3;
-                        float acc[3];
+                        const float* sh_g = shs + (size_t)i * M * 3;
+                        float sh[NB * 3], u[3], rgb[3];
+                        view_dir(cam, px_, py_, pz_, u);
 #pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) acc[ch] = bk[0] * sh[ch];
-#pragma unroll
-                        for (int k = 1; k < NB; ++k)
-#pragma unroll
-                            for (int ch = 0; ch < 3; ++ch) acc[ch] = acc[ch] + bk[k] * sh[3 * k + ch];
-#pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) {
-                            acc[ch] = acc[ch] + 0.5f;
-                            if (acc[ch] < 0.f) clampbits |= (1u << ch);
-                            acc[ch] = fmaxf(acc[ch], 0.f);
-                        }
-                        rgbd.x = acc[0]; rgbd.y = acc[1]; rgbd.z = acc[2];
+                        for (int k = 0; k < NB * 3; ++k) sh[k] = sh_g[k];
+                        clampbits = sh_colour<DEG>(u, sh, rgb);
+                        rgbd.x = rgb[0]; rgbd.y = rgb[1]; rgbd.z = rgb[2];
                     }
                     rgbd.w = depth;
                 } else {
@@ -208,14 +344,7 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_kernel(
         }
         radii[i] = rad;
         g_depths[i] = depth;
-        {   // this lane's record into its wave's OUT slice (stored coalesced below: see preprocess_fwd_views_kernel)
-            const float2 ext = alpha_extent(con_o);
-            float* mine = rec_out + (int)threadIdx.x * REC_STRIDE;
-            *reinterpret_cast<float4*>(mine) = make_float4(pxy.x, pxy.y, depth, 0.f);
-            *reinterpret_cast<float4*>(mine + 4) = con_o;
-            *reinterpret_cast<float4*>(mine + 8) = rgbd;
-            *reinterpret_cast<float4*>(mine + 12) = make_float4(ext.x, ext.y, 0.f, 0.f);
-        }
+        stage_rec(rec_out, pxy, depth, con_o, rgbd);
         if (!cov3D_precomp) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) g_cov3D[6 * i + k] = c6[k];
@@ -224,31 +353,11 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_kernel(
         g_tiles[i] = tiles;
         g_clamped[i] = (uint8_t)clampbits;
     }
-    {   // 64 records = 4 KB contiguous: four coalesced 1 KB stores per wave instead of 64-line-stride float4 stores per lane
-        const int wave0 = (int)(threadIdx.x & ~63u), lane = (int)(threadIdx.x & 63u);
-        const int first = blockIdx.x * GDR_BLOCK + wave0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        const int nrec = min(GDR_WAVE, N - first);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = lane + GDR_WAVE * j, r = q >> 2, c = q & 3;
-            if (r < nrec) g_rec[4 * (size_t)first + q] = *reinterpret_cast<const float4*>(rec_out + (wave0 + r) * REC_STRIDE + 4 * c);
-        }
-    }
-    // block partial sum of tiles_touched -> block_sums[blockIdx.x] (feeds the scan, K2)
-    uint32_t v = tiles;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    store_wave_recs(rec_out, g_rec, N);
     __shared__ uint32_t wsum[GDR_BLOCK / GDR_WAVE];
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    wave_tiles_sum(tiles, wsum);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t bs = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        block_sums[blockIdx.x] = bs;
-        block_offs[blockIdx.x] = bs ? atomicAdd(num_rendered, bs) : 0u;  // this block's slice of the D duplicates
-    }
+    if (threadIdx.x == 0) publish_block_sum(wsum, block_sums, block_offs, num_rendered);
 }
 
 // ---------------------------------------------------------------------------------
@@ -304,8 +413,7 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_kernel(
     if (vis) {
         const float px_ = means3D[3 * i], py_ = means3D[3 * i + 1], pz_ = means3D[3 * i + 2];
         const float4 g2 = grad_rec[4 * i];          // mean2D x, y, |x|, |y|
-        float4 gconic = grad_rec[4 * i + 1];        // conic.xyz (K7 leaves the exact factors -1/2, -1, -1/2 to us), ddepth
-        gconic.x *= -0.5f; gconic.y = -gconic.y; gconic.z *= -0.5f;
+        const float4 gconic = grad_rec[4 * i + 1];  // conic.xyz (K7 leaves the exact factors -1/2, -1, -1/2 to us), ddepth
         const float4 gcolor = grad_rec[4 * i + 2];  // rgb, opacity
         {
             float dop = gcolor.w;
@@ -326,67 +434,20 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_kernel(
 #pragma unroll
         for (int k = 0; k < 6; ++k) c6[k] = cov3D[6 * i + k];
 
-        const float pvx = cam.v[0] * px_ + cam.v[4] * py_ + cam.v[8] * pz_ + cam.v[12];
-        const float pvy = cam.v[1] * px_ + cam.v[5] * py_ + cam.v[9] * pz_ + cam.v[13];
-        const float pvz = cam.v[2] * px_ + cam.v[6] * py_ + cam.v[10] * pz_ + cam.v[14];
-        Ewa e;
-        ewa(cam, pvx, pvy, pvz, c6, focal_x, focal_y, tanx, tany, e);
-        const float a = e.a, b = e.b, c = e.c;
-        const float det = a * c - b * b;
-        float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
-        if (det * det != 0.f) {
-            const float d2 = 1.f / (det * det);
-            dL_da = d2 * (-c * c * gconic.x + b * c * gconic.y - b * b * gconic.z);
-            dL_db = d2 * (2.f * b * c * gconic.x - (a * c + b * b) * gconic.y + 2.f * a * b * gconic.z);
-            dL_dc = d2 * (-b * b * gconic.x + a * b * gconic.y - a * a * gconic.z);
-            const float* A0 = e.A0;
-            const float* A1 = e.A1;
-            dcov[0] = A0[0] * A0[0] * dL_da + A0[0] * A1[0] * dL_db + A1[0] * A1[0] * dL_dc;
-            dcov[3] = A0[1] * A0[1] * dL_da + A0[1] * A1[1] * dL_db + A1[1] * A1[1] * dL_dc;
-            dcov[5] = A0[2] * A0[2] * dL_da + A0[2] * A1[2] * dL_db + A1[2] * A1[2] * dL_dc;
-            dcov[1] = 2.f * A0[0] * A0[1] * dL_da + (A0[0] * A1[1] + A0[1] * A1[0]) * dL_db + 2.f * A1[0] * A1[1] * dL_dc;
-            dcov[2] = 2.f * A0[0] * A0[2] * dL_da + (A0[0] * A1[2] + A0[2] * A1[0]) * dL_db + 2.f * A1[0] * A1[2] * dL_dc;
-            dcov[4] = 2.f * A0[1] * A0[2] * dL_da + (A0[1] * A1[2] + A0[2] * A1[1]) * dL_db + 2.f * A1[1] * A1[2] * dL_dc;
+        ConicGrad cg;
+        conic_backward(cam, px_, py_, pz_, c6, focal_x, focal_y, tanx, tany, g2, gconic, cg);
+        if (cg.has_cov) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) dcov[k] = cg.dcov[k];
         }
-        float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float dA0 = 2.f * dL_da * e.v0[k] + dL_db * e.v1[k];
-            const float dA1 = 2.f * dL_dc * e.v1[k] + dL_db * e.v0[k];
-            dJ00 += dA0 * cam.v[4 * k + 0];
-            dJ02 += dA0 * cam.v[4 * k + 2];
-            dJ11 += dA1 * cam.v[4 * k + 1];
-            dJ12 += dA1 * cam.v[4 * k + 2];
+            dmean[k] = cg.dmean_ewa[k];
+            dmean[k] += cg.dmean_proj[k];
+            if (!(flags & GDR_IN_NO_DEPTH_TO_MEAN)) dmean[k] += cam.v[4 * k + 2] * gconic.w;
         }
-        const float tz1 = 1.f / e.tz, tz2 = tz1 * tz1, tz3 = tz2 * tz1;
-        const float dtx = e.xmul * (-focal_x * tz2 * dJ02);
-        const float dty = e.ymul * (-focal_y * tz2 * dJ12);
-        const float dtz = -focal_x * tz2 * dJ00 - focal_y * tz2 * dJ11 +
-                          (2.f * focal_x * e.tx) * tz3 * dJ02 + (2.f * focal_y * e.ty) * tz3 * dJ12;
-        // projection of the mean (A.5-ii) and depth path (A.5-iii)
-        const float mhx = cam.p[0] * px_ + cam.p[4] * py_ + cam.p[8] * pz_ + cam.p[12];
-        const float mhy = cam.p[1] * px_ + cam.p[5] * py_ + cam.p[9] * pz_ + cam.p[13];
-        const float mhw = cam.p[3] * px_ + cam.p[7] * py_ + cam.p[11] * pz_ + cam.p[15];
-        const float m_w = 1.f / (mhw + 0.0000001f);
-        const float mul1 = mhx * m_w * m_w, mul2 = mhy * m_w * m_w;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            dmean[k] = cam.v[4 * k + 0] * dtx + cam.v[4 * k + 1] * dty + cam.v[4 * k + 2] * dtz;
-            dmean[k] += (cam.p[4 * k + 0] * m_w - cam.p[4 * k + 3] * mul1) * g2.x +
-                        (cam.p[4 * k + 1] * m_w - cam.p[4 * k + 3] * mul2) * g2.y;
-            if (!(flags & GDR_IN_NO_DEPTH_TO_MEAN)) dmean[k] += cam.v[4 * k + 2] * gconic.w;  // risk R1 switch
-        }
-        // SH backward (A.5-iv)
         if (!colors_precomp) {
-            float dx = px_ - cam.c[0], dy = py_ - cam.c[1], dz = pz_ - cam.c[2];
-            const float inv = 1.f / sqrtf((dx * dx + dy * dy) + dz * dz);
-            const float ux = dx * inv, uy = dy * inv, uz = dz * inv;
-            float bk[NB], bx[NB], by[NB], bz[NB];
-            sh_basis<DEG>(ux, uy, uz, bk);
-            sh_basis_grad<DEG>(ux, uy, uz, bx, by, bz);
             const uint32_t cl = g_clamped[i];
-            const float g[3] = {(cl & 1u) ? 0.f : gcolor.x, (cl & 2u) ? 0.f : gcolor.y,
-                                (cl & 4u) ? 0.f : gcolor.z};
             const float* sh_g = shs + (size_t)i * M * 3;
             float sh[NB * 3];
             if (STAGED) {
@@ -399,17 +460,9 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_kernel(
 #pragma unroll
                 for (int k = 0; k < NB * 3; ++k) sh[k] = sh_g[k];
             }
-            float ddx = 0.f, ddy = 0.f, ddz = 0.f;
-#pragma unroll
-            for (int k = 0; k < NB; ++k) {
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const float sg = sh[3 * k + ch] * g[ch];
-                    ddx += bx[k] * sg;
-                    ddy += by[k] * sg;
-                    ddz += bz[k] * sg;
-                }
-            }
+            float u[3], bk[NB], g[3], dm[3];
+            const float inv = view_dir(cam, px_, py_, pz_, u);
+            sh_backward<DEG>(u, inv, sh, gcolor.x, gcolor.y, gcolor.z, cl, bk, g, dm);
             // dL/dsh[k][ch] = b_k g_ch: written (or added) as whole 16-byte chunks when the SH row
             // of a Gaussian is 16-byte aligned (M*12 % 16 == 0: deg 1 and 3), else scalar
             if (STAGED) {  // the gradient row replaces the SH row this thread owns; written out coalesced after body()
@@ -442,10 +495,8 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_kernel(
                     for (int k = NB; k < M; ++k)
                         for (int ch = 0; ch < 3; ++ch) dsh[3 * k + ch] = 0.f;
             }
-            const float dot = ux * ddx + uy * ddy + uz * ddz;
-            dmean[0] += (ddx - ux * dot) * inv;
-            dmean[1] += (ddy - uy * dot) * inv;
-            dmean[2] += (ddz - uz * dot) * inv;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dmean[k] += dm[k];
         } else if (dL_dcolors) {
             if (accumulate) {
                 dL_dcolors[3 * i] += gcolor.x; dL_dcolors[3 * i + 1] += gcolor.y; dL_dcolors[3 * i + 2] += gcolor.z;
@@ -460,41 +511,7 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_kernel(
             float inv_n = 1.f;
             if (flags & GDR_IN_RAW_ROTATIONS) q = act_normalize(q, &inv_n);
             if (flags & GDR_IN_RAW_SCALES) { sc0 = expf(sc0); sc1 = expf(sc1); sc2 = expf(sc2); }
-            float R[9];
-            quat_to_R(q.x, q.y, q.z, q.w, R);
-            const float s[3] = {scale_modifier * sc0, scale_modifier * sc1, scale_modifier * sc2};
-            const float Gs[9] = {dcov[0], 0.5f * dcov[1], 0.5f * dcov[2], 0.5f * dcov[1], dcov[3],
-                                 0.5f * dcov[4], 0.5f * dcov[2], 0.5f * dcov[4], dcov[5]};
-            float dR[9];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                float ds = 0.f;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int l = 0; l < 3; ++l) acc += Gs[3 * r + l] * (R[3 * l + k] * s[k]);
-                    const float dM = 2.f * acc;
-                    ds += R[3 * r + k] * dM;
-                    dR[3 * r + k] = s[k] * dM;
-                }
-                dscale[k] = scale_modifier * ds;
-            }
-            const float qr = q.x, qx = q.y, qy = q.z, qz = q.w;
-#define G_(r_, c_) dR[3 * (r_) + (c_)]
-            drot.x = 2.f * (-qz * G_(0, 1) + qy * G_(0, 2) + qz * G_(1, 0) - qx * G_(1, 2) - qy * G_(2, 0) + qx * G_(2, 1));
-            drot.y = 2.f * (qy * G_(0, 1) + qz * G_(0, 2) + qy * G_(1, 0) - 2.f * qx * G_(1, 1) - qr * G_(1, 2) + qz * G_(2, 0) + qr * G_(2, 1) - 2.f * qx * G_(2, 2));
-            drot.z = 2.f * (-2.f * qy * G_(0, 0) + qx * G_(0, 1) + qr * G_(0, 2) + qx * G_(1, 0) + qz * G_(1, 2) - qr * G_(2, 0) + qz * G_(2, 1) - 2.f * qy * G_(2, 2));
-            drot.w = 2.f * (-2.f * qz * G_(0, 0) - qr * G_(0, 1) + qx * G_(0, 2) + qr * G_(1, 0) - 2.f * qz * G_(1, 1) + qy * G_(1, 2) + qx * G_(2, 0) + qy * G_(2, 1));
-#undef G_
-            if (flags & GDR_IN_RAW_SCALES) {  // d exp = s
-                dscale[0] *= sc0; dscale[1] *= sc1; dscale[2] *= sc2;
-            }
-            if (flags & GDR_IN_RAW_ROTATIONS) {  // d (q/|q|) = (I - q^ q^T) / |q|
-                const float dot = (q.x * drot.x + q.y * drot.y) + (q.z * drot.z + q.w * drot.w);
-                drot = make_float4((drot.x - q.x * dot) * inv_n, (drot.y - q.y * dot) * inv_n,
-                                   (drot.z - q.z * dot) * inv_n, (drot.w - q.w * dot) * inv_n);
-            }
+            cov3d_backward(q, inv_n, sc0, sc1, sc2, scale_modifier, dcov, flags, dscale, drot);
         }
     } else {
         dL_dmean2D[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -551,8 +568,19 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_kernel(
 // the view-independent work is done once: inputs (236 B at SH degree 3) are read once instead
 // of V times, cov3D is computed/stored once, and in the backward the per-view partial
 // gradients are summed in registers and every output is written once (no read-modify-write
-// passes, no V-fold SH gradient traffic).  Per-view arithmetic is expression-for-expression the
-// single-view kernels', so integer intermediates stay bit-identical.
+// passes, no V-fold SH gradient traffic).
+// K1: per-view arithmetic IS the single-view kernel's.  Both call the same helpers in the same
+// order (cov3d_of, project, ewa, cov2d_det, splat_radius, ndc2pix, conic_of, stage_rec /
+// store_wave_recs above; to_view, tile_rect, view_dir, sh_colour and the tile sums in
+// device_math.h), so integer intermediates are bit-identical by construction.
+// K9: shares to_view, ewa, project, conic_grad_of, cov2d_grad, view_dir, sh_backward and quat_grad
+// with the single-view kernel (which reaches them through conic_backward / cov3d_backward).  The
+// rest of its per-view chain (cov2D -> cov3D terms, EWA Jacobian -> mean, scale / rotation
+// Jacobian, the normalisation derivative) is still written out here, expression for expression
+// that of conic_backward / cov3d_backward: calling those two, or any helper that hands back an
+// array, moved the register allocation of the degree-1 instantiations from 119 / 121 to 128..142
+// VGPRs, over the 128 that four waves per SIMD allow (see the dispatch note in
+// launch_preprocess_bwd_views); helpers that return a scalar or a float3 / float4 left it alone.
 // =================================================================================
 struct FwdView {
     const float* view; const float* proj; const float* campos;
@@ -579,7 +607,6 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_views_kernel(
     constexpr int NB = (DEG + 1) * (DEG + 1);
     constexpr int ROWF = 3 * NB;
     using RS = RowStage<STAGED ? ROWF : 4>;
-    constexpr int REC_STRIDE = 20;   // floats per record in the OUT slice: (stride / 4) odd -> 16-byte accesses rotate through the banks
     // IN staging only where the rows are small (degree 1: 12 floats, 20 KB per workgroup).  At degree 3 the 53 KB it takes
     // leave two workgroups per CU instead of three and K1 runs 30 % SLOWER than with the strided loads (same-box A/B,
     // profiles/r05_ab_k1_staged.txt: C4 286 -> 378 us, C2 46 -> 54 us): the OUT staging alone is kept there.
@@ -615,17 +642,7 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_views_kernel(
         float sc0 = scales[3 * i], sc1 = scales[3 * i + 1], sc2 = scales[3 * i + 2];
         if (flags & GDR_IN_RAW_ROTATIONS) { float inv_n; q = act_normalize(q, &inv_n); }
         if (flags & GDR_IN_RAW_SCALES) { sc0 = expf(sc0); sc1 = expf(sc1); sc2 = expf(sc2); }
-        float R[9], Mm[9];
-        quat_to_R(q.x, q.y, q.z, q.w, R);
-        const float s[3] = {scale_modifier * sc0, scale_modifier * sc1, scale_modifier * sc2};
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) Mm[r * 3 + k] = R[r * 3 + k] * s[k];
-#define SIG(a_, b_) ((Mm[a_ * 3 + 0] * Mm[b_ * 3 + 0] + Mm[a_ * 3 + 1] * Mm[b_ * 3 + 1]) + Mm[a_ * 3 + 2] * Mm[b_ * 3 + 2])
-        c6[0] = SIG(0, 0); c6[1] = SIG(0, 1); c6[2] = SIG(0, 2);
-        c6[3] = SIG(1, 1); c6[4] = SIG(1, 2); c6[5] = SIG(2, 2);
-#undef SIG
+        cov3d_of(q, sc0, sc1, sc2, scale_modifier, c6);
 #pragma unroll
         for (int k = 0; k < 6; ++k) g_cov3D[6 * i + k] = c6[k];
     }
@@ -642,41 +659,27 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_views_kernel(
             float4 rgbd = make_float4(0.f, 0.f, 0.f, 0.f);
             int4 rect = make_int4(0, 0, 0, 0);
             uint32_t clampbits = 0;
-            const float pvx = cam.v[0] * px_ + cam.v[4] * py_ + cam.v[8] * pz_ + cam.v[12];
-            const float pvy = cam.v[1] * px_ + cam.v[5] * py_ + cam.v[9] * pz_ + cam.v[13];
-            const float pvz = cam.v[2] * px_ + cam.v[6] * py_ + cam.v[10] * pz_ + cam.v[14];
-            bool ok = pvz > 0.2f;
+            const float3 pv = to_view(cam, px_, py_, pz_);
+            bool ok = pv.z > 0.2f;
             if (ok) {
-                const float phx = cam.p[0] * px_ + cam.p[4] * py_ + cam.p[8] * pz_ + cam.p[12];
-                const float phy = cam.p[1] * px_ + cam.p[5] * py_ + cam.p[9] * pz_ + cam.p[13];
-                const float phw = cam.p[3] * px_ + cam.p[7] * py_ + cam.p[11] * pz_ + cam.p[15];
-                const float p_w = 1.0f / (phw + 0.0000001f);
-                const float ppx = phx * p_w, ppy = phy * p_w;
+                const float3 ph = project(cam, px_, py_, pz_);
+                const float ppx = ph.x * ph.z, ppy = ph.y * ph.z;
                 Ewa e;
-                ewa(cam, pvx, pvy, pvz, c6, fv.fx, fv.fy, fv.tanx, fv.tany, e);
-                const float det = e.a * e.c - e.b * e.b;
+                ewa(cam, pv.x, pv.y, pv.z, c6, fv.fx, fv.fy, fv.tanx, fv.tany, e);
+                const float det = cov2d_det(e);
                 ok = det != 0.f;
                 if (ok) {
                     const float det_inv = 1.f / det;
-                    const float mid = 0.5f * (e.a + e.c);
-                    const float disc = sqrtf(fmaxf(0.1f, mid * mid - det));
-                    const float lambda1 = mid + disc, lambda2 = mid - disc;
-                    const float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
-                    const float sx = ((ppx + 1.0f) * (float)W - 1.0f) * 0.5f;
-                    const float sy = ((ppy + 1.0f) * (float)H - 1.0f) * 0.5f;
-                    const int r_i = (int)my_radius;
-                    const float rf = (float)r_i;
-                    rect.x = min(gx, max(0, (int)((sx - rf) / (float)GDR_TILE)));
-                    rect.y = min(gy, max(0, (int)((sy - rf) / (float)GDR_TILE)));
-                    rect.z = min(gx, max(0, (int)((sx + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
-                    rect.w = min(gy, max(0, (int)((sy + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
-                    tiles = (uint32_t)((rect.z - rect.x) * (rect.w - rect.y));
+                    const int r_i = splat_radius(e.a, e.c, det);
+                    const float sx = ndc2pix(ppx, W), sy = ndc2pix(ppy, H);
+                    tiles = tile_rect(sx, sy, r_i, gx, gy, rect);
                     ok = tiles != 0;
                     if (ok) {
                         rad = r_i;
-                        depth = pvz;
+                        depth = pv.z;
                         pxy = make_float2(sx, sy);
-                        con_o = make_float4(e.c * det_inv, -e.b * det_inv, e.a * det_inv, op);
+                        const float3 conic = conic_of(e, det_inv);
+                        con_o = make_float4(conic.x, conic.y, conic.z, op);
                         if (!sh_loaded) {  // first view in which this Gaussian is visible
                             const float* src = shs + (size_t)i * M * 3;
                             if ((M * 3) % 4 == 0) {
@@ -693,25 +696,10 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_views_kernel(
                             }
                             sh_loaded = true;
                         }
-                        float dx = px_ - cam.c[0], dy = py_ - cam.c[1], dz = pz_ - cam.c[2];
-                        const float inv = 1.f / sqrtf((dx * dx + dy * dy) + dz * dz);
-                        dx *= inv; dy *= inv; dz *= inv;
-                        float bk[NB];
-                        sh_basis<DEG>(dx, dy, dz, bk);
-                        float acc[3];
-#pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) acc[ch] = bk[0] * sh[ch];
-#pragma unroll
-                        for (int k = 1; k < NB; ++k)
-#pragma unroll
-                            for (int ch = 0; ch < 3; ++ch) acc[ch] = acc[ch] + bk[k] * sh[3 * k + ch];
-#pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) {
-                            acc[ch] = acc[ch] + 0.5f;
-                            if (acc[ch] < 0.f) clampbits |= (1u << ch);
-                            acc[ch] = fmaxf(acc[ch], 0.f);
-                        }
-                        rgbd = make_float4(acc[0], acc[1], acc[2], depth);
+                        float u[3], rgb[3];
+                        view_dir(cam, px_, py_, pz_, u);
+                        clampbits = sh_colour<DEG>(u, sh, rgb);
+                        rgbd = make_float4(rgb[0], rgb[1], rgb[2], depth);
                     } else {
                         rect = make_int4(0, 0, 0, 0);
                     }
@@ -724,43 +712,20 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_fwd_views_kernel(
             fv.rect[i] = rect;
             fv.tiles[i] = tiles;
             fv.clamped[i] = (uint8_t)clampbits;
-            if (STAGED) {       // this lane's record into the wave's OUT slice
-                const float2 ext = alpha_extent(con_o);
-                float* mine = lds_rows + (int)threadIdx.x * REC_STRIDE;
-                *reinterpret_cast<float4*>(mine) = make_float4(pxy.x, pxy.y, depth, 0.f);
-                *reinterpret_cast<float4*>(mine + 4) = con_o;
-                *reinterpret_cast<float4*>(mine + 8) = rgbd;
-                *reinterpret_cast<float4*>(mine + 12) = make_float4(ext.x, ext.y, 0.f, 0.f);
-            }
+            if (STAGED) stage_rec(lds_rows, pxy, depth, con_o, rgbd);
         }
-        if (STAGED) {           // 64 records = 4 KB contiguous in the view's record array: four coalesced 1 KB stores per wave
-            const int wave0 = (int)(threadIdx.x & ~63u), lane = (int)(threadIdx.x & 63u);
-            const int first = blockIdx.x * GDR_BLOCK + wave0;          // first Gaussian of this wave
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            const int nrec = min(GDR_WAVE, N - first);                   // (<= 0 for a wave past the end)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int q = lane + GDR_WAVE * j;                       // float4 index inside the wave's 4 KB span
-                const int r = q >> 2, c = q & 3;
-                if (r < nrec)
-                    fv.rec[4 * (size_t)first + q] = *reinterpret_cast<const float4*>(lds_rows + (wave0 + r) * REC_STRIDE + 4 * c);
-            }
+        if (STAGED) {
+            store_wave_recs(lds_rows, fv.rec, N);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_wave_barrier();                             // the slice is free for the next view
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
-        uint32_t t = tiles;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-        if ((threadIdx.x & 63) == 0) wsum[v][threadIdx.x >> 6] = t;
+        wave_tiles_sum(tiles, wsum[v]);
     }
     __syncthreads();
     if ((int)threadIdx.x < a.V) {
-        const uint32_t bs = wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
-        a.v[threadIdx.x].block_sums[blockIdx.x] = bs;
-        a.v[threadIdx.x].block_offs[blockIdx.x] = bs ? atomicAdd(a.v[threadIdx.x].num_rendered, bs) : 0u;
+        const FwdView& fv = a.v[threadIdx.x];
+        publish_block_sum(wsum[threadIdx.x], fv.block_sums, fv.block_offs, fv.num_rendered);
     }
 }
 
@@ -864,22 +829,18 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_views_kernel(
             g2 = bv.grad_rec[4 * i]; gconic = bv.grad_rec[4 * i + 1]; gcolor = bv.grad_rec[4 * i + 2];
             cl_v = bv.clamped[i];
         }
-        gconic.x *= -0.5f; gconic.y = -gconic.y; gconic.z *= -0.5f;   // (K7 leaves these exact factors to us)
+        gconic = conic_grad_of(gconic);
         dm2 = make_float4(dm2.x + g2.x, dm2.y + g2.y, dm2.z + g2.z, dm2.w + g2.w);
         dop += gcolor.w;
-        const float pvx = cam.v[0] * px_ + cam.v[4] * py_ + cam.v[8] * pz_ + cam.v[12];
-        const float pvy = cam.v[1] * px_ + cam.v[5] * py_ + cam.v[9] * pz_ + cam.v[13];
-        const float pvz = cam.v[2] * px_ + cam.v[6] * py_ + cam.v[10] * pz_ + cam.v[14];
+        const float3 pv = to_view(cam, px_, py_, pz_);
         Ewa e;
-        ewa(cam, pvx, pvy, pvz, c6, bv.fx, bv.fy, bv.tanx, bv.tany, e);
+        ewa(cam, pv.x, pv.y, pv.z, c6, bv.fx, bv.fy, bv.tanx, bv.tany, e);
         const float ea = e.a, eb = e.b, ec = e.c;
         const float det = ea * ec - eb * eb;
         float dL_da = 0.f, dL_db = 0.f, dL_dc = 0.f;
         if (det * det != 0.f) {
-            const float d2 = 1.f / (det * det);
-            dL_da = d2 * (-ec * ec * gconic.x + eb * ec * gconic.y - eb * eb * gconic.z);
-            dL_db = d2 * (2.f * eb * ec * gconic.x - (ea * ec + eb * eb) * gconic.y + 2.f * ea * eb * gconic.z);
-            dL_dc = d2 * (-eb * eb * gconic.x + ea * eb * gconic.y - ea * ea * gconic.z);
+            const float3 d = cov2d_grad(ea, eb, ec, det, gconic);
+            dL_da = d.x; dL_db = d.y; dL_dc = d.z;
             const float* A0 = e.A0;
             const float* A1 = e.A1;
             dcov[0] += A0[0] * A0[0] * dL_da + A0[0] * A1[0] * dL_db + A1[0] * A1[0] * dL_dc;
@@ -904,11 +865,9 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_views_kernel(
         const float dty = e.ymul * (-bv.fy * tz2 * dJ12);
         const float dtz = -bv.fx * tz2 * dJ00 - bv.fy * tz2 * dJ11 + (2.f * bv.fx * e.tx) * tz3 * dJ02 +
                           (2.f * bv.fy * e.ty) * tz3 * dJ12;
-        const float mhx = cam.p[0] * px_ + cam.p[4] * py_ + cam.p[8] * pz_ + cam.p[12];
-        const float mhy = cam.p[1] * px_ + cam.p[5] * py_ + cam.p[9] * pz_ + cam.p[13];
-        const float mhw = cam.p[3] * px_ + cam.p[7] * py_ + cam.p[11] * pz_ + cam.p[15];
-        const float m_w = 1.f / (mhw + 0.0000001f);
-        const float mul1 = mhx * m_w * m_w, mul2 = mhy * m_w * m_w;
+        const float3 mh = project(cam, px_, py_, pz_);
+        const float m_w = mh.z;
+        const float mul1 = mh.x * m_w * m_w, mul2 = mh.y * m_w * m_w;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             dmean[k] += cam.v[4 * k + 0] * dtx + cam.v[4 * k + 1] * dty + cam.v[4 * k + 2] * dtz;
@@ -917,16 +876,6 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_views_kernel(
             if (!(flags & GDR_IN_NO_DEPTH_TO_MEAN)) dmean[k] += cam.v[4 * k + 2] * gconic.w;  // risk R1 switch
         }
         {   // SH backward
-            float dx = px_ - cam.c[0], dy = py_ - cam.c[1], dz = pz_ - cam.c[2];
-            const float inv = 1.f / sqrtf((dx * dx + dy * dy) + dz * dz);
-            const float ux = dx * inv, uy = dy * inv, uz = dz * inv;
-            float bk[NB], bx[NB], by[NB], bz[NB];
-            sh_basis<DEG>(ux, uy, uz, bk);
-            sh_basis_grad<DEG>(ux, uy, uz, bx, by, bz);
-            const uint32_t cl = cl_v;
-            const float g[3] = {(cl & 1u) ? 0.f : gcolor.x, (cl & 2u) ? 0.f : gcolor.y,
-                                (cl & 4u) ? 0.f : gcolor.z};
-            float ddx = 0.f, ddy = 0.f, ddz = 0.f;
             float shr[NB * 3];  // this view's copy of the SH row: 16-byte LDS reads when staged
             if (STAGED) {
 #pragma unroll
@@ -938,21 +887,15 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_views_kernel(
 #pragma unroll
                 for (int k = 0; k < NB * 3; ++k) shr[k] = sh(k);
             }
+            float u[3], bk[NB], g[3], dm[3];
+            const float inv = view_dir(cam, px_, py_, pz_, u);
+            sh_backward<DEG>(u, inv, shr, gcolor.x, gcolor.y, gcolor.z, cl_v, bk, g, dm);
 #pragma unroll
-            for (int k = 0; k < NB; ++k) {
+            for (int k = 0; k < NB; ++k)
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const float sg = shr[3 * k + ch] * g[ch];
-                    dsh[3 * k + ch] += bk[k] * g[ch];
-                    ddx += bx[k] * sg;
-                    ddy += by[k] * sg;
-                    ddz += bz[k] * sg;
-                }
-            }
-            const float dot = ux * ddx + uy * ddy + uz * ddz;
-            dmean[0] += (ddx - ux * dot) * inv;
-            dmean[1] += (ddy - uy * dot) * inv;
-            dmean[2] += (ddz - uz * dot) * inv;
+                for (int ch = 0; ch < 3; ++ch) dsh[3 * k + ch] += bk[k] * g[ch];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dmean[k] += dm[k];
         }
     }
     if (!STAGED && accumulate && !any_vis) return;
@@ -988,13 +931,7 @@ __global__ __launch_bounds__(GDR_BLOCK) void preprocess_bwd_views_kernel(
             }
             dscale[k] = scale_modifier * ds;
         }
-        const float qr = q.x, qx = q.y, qy = q.z, qz = q.w;
-#define G_(r_, c_) dR[3 * (r_) + (c_)]
-        drot.x = 2.f * (-qz * G_(0, 1) + qy * G_(0, 2) + qz * G_(1, 0) - qx * G_(1, 2) - qy * G_(2, 0) + qx * G_(2, 1));
-        drot.y = 2.f * (qy * G_(0, 1) + qz * G_(0, 2) + qy * G_(1, 0) - 2.f * qx * G_(1, 1) - qr * G_(1, 2) + qz * G_(2, 0) + qr * G_(2, 1) - 2.f * qx * G_(2, 2));
-        drot.z = 2.f * (-2.f * qy * G_(0, 0) + qx * G_(0, 1) + qr * G_(0, 2) + qx * G_(1, 0) + qz * G_(1, 2) - qr * G_(2, 0) + qz * G_(2, 1) - 2.f * qy * G_(2, 2));
-        drot.w = 2.f * (-2.f * qz * G_(0, 0) - qr * G_(0, 1) + qx * G_(0, 2) + qr * G_(1, 0) - 2.f * qz * G_(1, 1) + qy * G_(1, 2) + qx * G_(2, 0) + qy * G_(2, 1));
-#undef G_
+        drot = quat_grad(q, dR);
         if (flags & GDR_IN_RAW_SCALES) { dscale[0] *= sc0; dscale[1] *= sc1; dscale[2] *= sc2; }
         if (flags & GDR_IN_RAW_ROTATIONS) {
             const float dot = (q.x * drot.x + q.y * drot.y) + (q.z * drot.z + q.w * drot.w);
@@ -1171,8 +1108,8 @@ hipError_t launch_preprocess_bwd_views(int V, const gdr_settings* s, const gdr_i
     }
     const int grid = div_up(N, GDR_BLOCK);
     // record prefetch (see the kernel): degree 3 only, where K9 runs at 2 waves per SIMD and a view's record has to be on
-    // its way while the view before is worked on; at degree 1 the extra registers cost a wave per SIMD (136 / 130 VGPRs
-    // with it against 121 / 119 without: 3 waves instead of 4; round 5 measured C3 82 -> 90 us with it)
+    // its way while the view before is worked on; at degree 1 the extra registers cost a wave per SIMD (132 / 130 VGPRs
+    // unstaged / staged with it against 121 / 119 without: 3 waves instead of 4; round 5 measured C3 82 -> 90 us with it)
     static const bool prefetch = getenv("GDR_K9_PREFETCH") ? atoi(getenv("GDR_K9_PREFETCH")) != 0 : true;
 #define GDR_K9V(DEG_, ST_)                                                                                  \
     if (prefetch && V > 1 && DEG_ == 3)                                                                     \

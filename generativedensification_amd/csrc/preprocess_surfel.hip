@@ -74,6 +74,49 @@ __device__ __forceinline__ void alpha_box(const SurfelT& T, float cx, float cy, 
     }
 }
 
+// The rest of the surfel arithmetic, each expression tree defined once for the single-view and the multi-view kernels
+// (what the 3DGS path shares as well is in device_math.h).
+
+// splat normal (third column of R) in view space, and minus its dot product with the view-space mean: > 0 where the
+// splat faces the camera as it is, < 0 where K1s flips the normal (mult = -1), 0 where it is seen edge-on (culled)
+__device__ __forceinline__ void surfel_normal(const Cam& cam, const float (&R)[9], float (&n)[3]) {
+    n[0] = (cam.v[0] * R[2] + cam.v[4] * R[5]) + cam.v[8] * R[8];
+    n[1] = (cam.v[1] * R[2] + cam.v[5] * R[5]) + cam.v[9] * R[8];
+    n[2] = (cam.v[2] * R[2] + cam.v[6] * R[5]) + cam.v[10] * R[8];
+}
+__device__ __forceinline__ float surfel_cosv(float3 pv, const float (&n)[3]) {
+    return -((pv.x * n[0] + pv.y * n[1]) + pv.z * n[2]);
+}
+
+// 3-sigma bounding box (oracle surfel_aabb) -> centre and integer radius; false where T is degenerate
+__device__ __forceinline__ bool surfel_aabb(const SurfelT& Tl, float& cx, float& cy, int& r_i) {
+    const float t0 = 9.f, t2 = -1.f;
+    const float d = (t0 * Tl.Tw[0] * Tl.Tw[0] + t0 * Tl.Tw[1] * Tl.Tw[1]) + t2 * Tl.Tw[2] * Tl.Tw[2];
+    if (!(d != 0.f)) return false;
+    const float inv_d = 1.f / d;
+    const float f0 = t0 * inv_d, f2 = t2 * inv_d;
+    cx = (f0 * Tl.Tu[0] * Tl.Tw[0] + f0 * Tl.Tu[1] * Tl.Tw[1]) + f2 * Tl.Tu[2] * Tl.Tw[2];
+    cy = (f0 * Tl.Tv[0] * Tl.Tw[0] + f0 * Tl.Tv[1] * Tl.Tw[1]) + f2 * Tl.Tv[2] * Tl.Tw[2];
+    const float hx0 = cx * cx - ((f0 * Tl.Tu[0] * Tl.Tu[0] + f0 * Tl.Tu[1] * Tl.Tu[1]) + f2 * Tl.Tu[2] * Tl.Tu[2]);
+    const float hy0 = cy * cy - ((f0 * Tl.Tv[0] * Tl.Tv[0] + f0 * Tl.Tv[1] * Tl.Tv[1]) + f2 * Tl.Tv[2] * Tl.Tv[2]);
+    const float ex = sqrtf(fmaxf(1e-4f, hx0)), ey = sqrtf(fmaxf(1e-4f, hy0));
+    const float my_radius = ceilf(fmaxf(fmaxf(ex, ey), 3.f * GSR_FILTER_SIZE));
+    r_i = (int)my_radius;
+    return true;
+}
+
+// the 96-byte render record of one surfel in one view (include/gsr.h)
+__device__ __forceinline__ void write_surfel_rec(float4* r, const SurfelT& T, const float (&cxy)[2], float op,
+                                                 const float (&nv)[3], const float (&rgb)[3], const float (&lo)[2],
+                                                 const float (&hi)[2]) {
+    r[0] = make_float4(T.Tu[0], T.Tu[1], T.Tu[2], cxy[0]);
+    r[1] = make_float4(T.Tv[0], T.Tv[1], T.Tv[2], cxy[1]);
+    r[2] = make_float4(T.Tw[0], T.Tw[1], T.Tw[2], op);
+    r[3] = make_float4(nv[0], nv[1], nv[2], rgb[0]);
+    r[4] = make_float4(rgb[1], rgb[2], lo[0], lo[1]);
+    r[5] = make_float4(hi[0], hi[1], 0.f, 0.f);
+}
+
 template <int DEG>
 __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_fwd_kernel(
     int N, int M, const float* __restrict__ means3D, const float* __restrict__ scales, float scale_modifier,
@@ -101,10 +144,8 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_fwd_kernel(
         float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
 
         const float p[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
-        const float pvx = cam.v[0] * p[0] + cam.v[4] * p[1] + cam.v[8] * p[2] + cam.v[12];
-        const float pvy = cam.v[1] * p[0] + cam.v[5] * p[1] + cam.v[9] * p[2] + cam.v[13];
-        const float pvz = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
-        bool ok = pvz > 0.2f;
+        const float3 pv = to_view(cam, p[0], p[1], p[2]);
+        bool ok = pv.z > 0.2f;
         if (ok) {
             SurfelT Tl;
             float n[3];
@@ -124,37 +165,20 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_fwd_kernel(
                 float R[9];
                 quat_to_R(q.x, q.y, q.z, q.w, R);
                 surfel_transmat(p, scale_modifier * sc0, scale_modifier * sc1, R, cam.p, W, H, Tl);
-                n[0] = (cam.v[0] * R[2] + cam.v[4] * R[5]) + cam.v[8] * R[8];
-                n[1] = (cam.v[1] * R[2] + cam.v[5] * R[5]) + cam.v[9] * R[8];
-                n[2] = (cam.v[2] * R[2] + cam.v[6] * R[5]) + cam.v[10] * R[8];
+                surfel_normal(cam, R, n);
             }
-            const float cosv = -((pvx * n[0] + pvy * n[1]) + pvz * n[2]);
+            const float cosv = surfel_cosv(pv, n);
             ok = cosv != 0.f;
             const float mult = cosv > 0.f ? 1.f : -1.f;
-            // 3-sigma bounding box (oracle surfel_aabb)
-            const float t0 = 9.f, t2 = -1.f;
-            const float d = (t0 * Tl.Tw[0] * Tl.Tw[0] + t0 * Tl.Tw[1] * Tl.Tw[1]) + t2 * Tl.Tw[2] * Tl.Tw[2];
-            ok = ok && d != 0.f;
+            float cx, cy;
+            int r_i;
+            ok = ok && surfel_aabb(Tl, cx, cy, r_i);
             if (ok) {
-                const float inv_d = 1.f / d;
-                const float f0 = t0 * inv_d, f2 = t2 * inv_d;
-                const float cx = (f0 * Tl.Tu[0] * Tl.Tw[0] + f0 * Tl.Tu[1] * Tl.Tw[1]) + f2 * Tl.Tu[2] * Tl.Tw[2];
-                const float cy = (f0 * Tl.Tv[0] * Tl.Tw[0] + f0 * Tl.Tv[1] * Tl.Tw[1]) + f2 * Tl.Tv[2] * Tl.Tw[2];
-                const float hx0 = cx * cx - ((f0 * Tl.Tu[0] * Tl.Tu[0] + f0 * Tl.Tu[1] * Tl.Tu[1]) + f2 * Tl.Tu[2] * Tl.Tu[2]);
-                const float hy0 = cy * cy - ((f0 * Tl.Tv[0] * Tl.Tv[0] + f0 * Tl.Tv[1] * Tl.Tv[1]) + f2 * Tl.Tv[2] * Tl.Tv[2]);
-                const float ex = sqrtf(fmaxf(1e-4f, hx0)), ey = sqrtf(fmaxf(1e-4f, hy0));
-                const float my_radius = ceilf(fmaxf(fmaxf(ex, ey), 3.f * GSR_FILTER_SIZE));
-                const int r_i = (int)my_radius;
-                const float rf = (float)r_i;
-                rect.x = min(gx, max(0, (int)((cx - rf) / (float)GDR_TILE)));
-                rect.y = min(gy, max(0, (int)((cy - rf) / (float)GDR_TILE)));
-                rect.z = min(gx, max(0, (int)((cx + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
-                rect.w = min(gy, max(0, (int)((cy + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
-                tiles = (uint32_t)((rect.z - rect.x) * (rect.w - rect.y));
+                tiles = tile_rect(cx, cy, r_i, gx, gy, rect);
                 ok = tiles != 0;
                 if (ok) {
                     rad = r_i;
-                    depth = pvz;
+                    depth = pv.z;
                     T = Tl;
                     cxy[0] = cx; cxy[1] = cy;
                     nv[0] = mult * n[0]; nv[1] = mult * n[1]; nv[2] = mult * n[2];
@@ -163,25 +187,13 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_fwd_kernel(
                     if (colors_precomp) {
                         rgb[0] = colors_precomp[3 * i]; rgb[1] = colors_precomp[3 * i + 1]; rgb[2] = colors_precomp[3 * i + 2];
                     } else {
-                        float dx = p[0] - cam.c[0], dy = p[1] - cam.c[1], dz = p[2] - cam.c[2];
-                        const float inv = 1.f / sqrtf((dx * dx + dy * dy) + dz * dz);
-                        dx *= inv; dy *= inv; dz *= inv;
                         constexpr int NB = (DEG + 1) * (DEG + 1);
-                        float bk[NB];
-                        sh_basis<DEG>(dx, dy, dz, bk);
-                        const float* sh = shs + (size_t)i * M * 3;
+                        const float* sh_g = shs + (size_t)i * M * 3;
+                        float sh[NB * 3], u[3];
+                        view_dir(cam, p[0], p[1], p[2], u);
 #pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) rgb[ch] = bk[0] * sh[ch];
-#pragma unroll
-                        for (int k = 1; k < NB; ++k)
-#pragma unroll
-                            for (int ch = 0; ch < 3; ++ch) rgb[ch] = rgb[ch] + bk[k] * sh[3 * k + ch];
-#pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) {
-                            rgb[ch] = rgb[ch] + 0.5f;
-                            if (rgb[ch] < 0.f) clampbits |= (1u << ch);
-                            rgb[ch] = fmaxf(rgb[ch], 0.f);
-                        }
+                        for (int k = 0; k < NB * 3; ++k) sh[k] = sh_g[k];
+                        clampbits = sh_colour<DEG>(u, sh, rgb);
                     }
                 } else {
                     rect = make_int4(0, 0, 0, 0);
@@ -191,28 +203,15 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_fwd_kernel(
         }
         radii[i] = rad;
         g_depths[i] = depth;
-        float4* r = g_rec + 6 * (size_t)i;
-        r[0] = make_float4(T.Tu[0], T.Tu[1], T.Tu[2], cxy[0]);
-        r[1] = make_float4(T.Tv[0], T.Tv[1], T.Tv[2], cxy[1]);
-        r[2] = make_float4(T.Tw[0], T.Tw[1], T.Tw[2], op);
-        r[3] = make_float4(nv[0], nv[1], nv[2], rgb[0]);
-        r[4] = make_float4(rgb[1], rgb[2], lo[0], lo[1]);
-        r[5] = make_float4(hi[0], hi[1], 0.f, 0.f);
+        write_surfel_rec(g_rec + 6 * (size_t)i, T, cxy, op, nv, rgb, lo, hi);
         g_rect[i] = rect;
         g_tiles[i] = tiles;
         g_clamped[i] = (uint8_t)clampbits;
     }
-    uint32_t v = tiles;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     __shared__ uint32_t wsum[GDR_BLOCK / GDR_WAVE];
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    wave_tiles_sum(tiles, wsum);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t bs = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        block_sums[blockIdx.x] = bs;
-        block_offs[blockIdx.x] = bs ? atomicAdd(num_rendered, bs) : 0u;
-    }
+    if (threadIdx.x == 0) publish_block_sum(wsum, block_sums, block_offs, num_rendered);
 }
 
 template <typename T>
@@ -363,20 +362,9 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_bwd_kernel(
             ds1 += R[3 * r + 1] * dv[1][r];
         }
         float dscale0 = scale_modifier * ds0, dscale1 = scale_modifier * ds1;
-        const float qr = q.x, qx = q.y, qy = q.z, qz = q.w;
-        float4 drot;
-#define G_(r_, c_) dR[3 * (r_) + (c_)]
-        drot.x = 2.f * (-qz * G_(0, 1) + qy * G_(0, 2) + qz * G_(1, 0) - qx * G_(1, 2) - qy * G_(2, 0) + qx * G_(2, 1));
-        drot.y = 2.f * (qy * G_(0, 1) + qz * G_(0, 2) + qy * G_(1, 0) - 2.f * qx * G_(1, 1) - qr * G_(1, 2) + qz * G_(2, 0) + qr * G_(2, 1) - 2.f * qx * G_(2, 2));
-        drot.z = 2.f * (-2.f * qy * G_(0, 0) + qx * G_(0, 1) + qr * G_(0, 2) + qx * G_(1, 0) + qz * G_(1, 2) - qr * G_(2, 0) + qz * G_(2, 1) - 2.f * qy * G_(2, 2));
-        drot.w = 2.f * (-2.f * qz * G_(0, 0) - qr * G_(0, 1) + qx * G_(0, 2) + qr * G_(1, 0) - 2.f * qz * G_(1, 1) + qy * G_(1, 2) + qx * G_(2, 0) + qy * G_(2, 1));
-#undef G_
-        if (flags & GDR_IN_RAW_SCALES) { dscale0 *= sc0; dscale1 *= sc1; }
-        if (flags & GDR_IN_RAW_ROTATIONS) {
-            const float dot = (q.x * drot.x + q.y * drot.y) + (q.z * drot.z + q.w * drot.w);
-            drot = make_float4((drot.x - q.x * dot) * inv_n, (drot.y - q.y * dot) * inv_n, (drot.z - q.z * dot) * inv_n,
-                               (drot.w - q.w * dot) * inv_n);
-        }
+        float4 drot = quat_grad(q, dR);
+        if (flags & GDR_IN_RAW_SCALES) { dscale0 = act_exp_grad(dscale0, sc0); dscale1 = act_exp_grad(dscale1, sc1); }
+        if (flags & GDR_IN_RAW_ROTATIONS) drot = act_normalize_grad(q, drot, inv_n);
         put(dL_dscale + 2 * i, dscale0, accumulate);
         put(dL_dscale + 2 * i + 1, dscale1, accumulate);
         if (accumulate) {
@@ -465,8 +453,12 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_bwd_kernel(
 // surfel and loops over the views: position / scales / quaternion / opacity (and their activations, the rotation
 // matrix) are read and computed once, the SH row is loaded once; in the backward the per-view gradients of the three
 // world-space vectors that build T (s_u t_u, s_v t_v, p), of the normal and of the SH block are summed in registers
-// and the scale / quaternion chain runs once.  Per-view arithmetic is expression-for-expression the single-view
-// kernels', so integer intermediates stay bit-identical.
+// and the scale / quaternion chain runs once.  K1s' per-view arithmetic IS the single-view kernel's: both call the same
+// helpers (surfel_transmat .. write_surfel_rec above and those of device_math.h), so integer intermediates are
+// bit-identical by construction.  K9s shares quat_grad and the activation derivatives (device_math.h); the rest of its
+// per-view chain (dL/dT decode, low-pass branch, T -> world vectors, normal, SH) is still written out in both backward
+// kernels, expression for expression: moved into helpers it cost registers (single-view 68 -> 76 VGPRs, 7 -> 6 waves per
+// SIMD; multi-view degree 3 244 -> 256 and 2 -> 1), so these two kernels keep their copies until that is understood.
 // =================================================================================
 struct SFwdView {
     const float* view; const float* proj; const float* campos;
@@ -515,42 +507,25 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_fwd_views_kernel(
             for (int k = 0; k < 3; ++k) T.Tu[k] = T.Tv[k] = T.Tw[k] = 0.f;
             float nv[3] = {0.f, 0.f, 0.f}, rgb[3] = {0.f, 0.f, 0.f}, cxy[2] = {0.f, 0.f}, opv = 0.f;
             float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
-            const float pvx = cam.v[0] * p[0] + cam.v[4] * p[1] + cam.v[8] * p[2] + cam.v[12];
-            const float pvy = cam.v[1] * p[0] + cam.v[5] * p[1] + cam.v[9] * p[2] + cam.v[13];
-            const float pvz = cam.v[2] * p[0] + cam.v[6] * p[1] + cam.v[10] * p[2] + cam.v[14];
-            bool ok = pvz > 0.2f;
+            const float3 pv = to_view(cam, p[0], p[1], p[2]);
+            bool ok = pv.z > 0.2f;
             if (ok) {
                 SurfelT Tl;
                 surfel_transmat(p, s0, s1, R, cam.p, W, H, Tl);
-                const float n[3] = {(cam.v[0] * R[2] + cam.v[4] * R[5]) + cam.v[8] * R[8],
-                                    (cam.v[1] * R[2] + cam.v[5] * R[5]) + cam.v[9] * R[8],
-                                    (cam.v[2] * R[2] + cam.v[6] * R[5]) + cam.v[10] * R[8]};
-                const float cosv = -((pvx * n[0] + pvy * n[1]) + pvz * n[2]);
+                float n[3];
+                surfel_normal(cam, R, n);
+                const float cosv = surfel_cosv(pv, n);
                 ok = cosv != 0.f;
                 const float mult = cosv > 0.f ? 1.f : -1.f;
-                const float t0 = 9.f, t2 = -1.f;
-                const float d = (t0 * Tl.Tw[0] * Tl.Tw[0] + t0 * Tl.Tw[1] * Tl.Tw[1]) + t2 * Tl.Tw[2] * Tl.Tw[2];
-                ok = ok && d != 0.f;
+                float cx, cy;
+                int r_i;
+                ok = ok && surfel_aabb(Tl, cx, cy, r_i);
                 if (ok) {
-                    const float inv_d = 1.f / d;
-                    const float f0 = t0 * inv_d, f2 = t2 * inv_d;
-                    const float cx = (f0 * Tl.Tu[0] * Tl.Tw[0] + f0 * Tl.Tu[1] * Tl.Tw[1]) + f2 * Tl.Tu[2] * Tl.Tw[2];
-                    const float cy = (f0 * Tl.Tv[0] * Tl.Tw[0] + f0 * Tl.Tv[1] * Tl.Tw[1]) + f2 * Tl.Tv[2] * Tl.Tw[2];
-                    const float hx0 = cx * cx - ((f0 * Tl.Tu[0] * Tl.Tu[0] + f0 * Tl.Tu[1] * Tl.Tu[1]) + f2 * Tl.Tu[2] * Tl.Tu[2]);
-                    const float hy0 = cy * cy - ((f0 * Tl.Tv[0] * Tl.Tv[0] + f0 * Tl.Tv[1] * Tl.Tv[1]) + f2 * Tl.Tv[2] * Tl.Tv[2]);
-                    const float ex = sqrtf(fmaxf(1e-4f, hx0)), ey = sqrtf(fmaxf(1e-4f, hy0));
-                    const float my_radius = ceilf(fmaxf(fmaxf(ex, ey), 3.f * GSR_FILTER_SIZE));
-                    const int r_i = (int)my_radius;
-                    const float rf = (float)r_i;
-                    rect.x = min(gx, max(0, (int)((cx - rf) / (float)GDR_TILE)));
-                    rect.y = min(gy, max(0, (int)((cy - rf) / (float)GDR_TILE)));
-                    rect.z = min(gx, max(0, (int)((cx + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
-                    rect.w = min(gy, max(0, (int)((cy + rf + (float)(GDR_TILE - 1)) / (float)GDR_TILE)));
-                    tiles = (uint32_t)((rect.z - rect.x) * (rect.w - rect.y));
+                    tiles = tile_rect(cx, cy, r_i, gx, gy, rect);
                     ok = tiles != 0;
                     if (ok) {
                         rad = r_i;
-                        depth = pvz;
+                        depth = pv.z;
                         T = Tl;
                         cxy[0] = cx; cxy[1] = cy;
                         nv[0] = mult * n[0]; nv[1] = mult * n[1]; nv[2] = mult * n[2];
@@ -562,23 +537,9 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_fwd_views_kernel(
                             for (int k = 0; k < NB * 3; ++k) sh[k] = src[k];
                             sh_loaded = true;
                         }
-                        float dx = p[0] - cam.c[0], dy = p[1] - cam.c[1], dz = p[2] - cam.c[2];
-                        const float inv = 1.f / sqrtf((dx * dx + dy * dy) + dz * dz);
-                        dx *= inv; dy *= inv; dz *= inv;
-                        float bk[NB];
-                        sh_basis<DEG>(dx, dy, dz, bk);
-#pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) rgb[ch] = bk[0] * sh[ch];
-#pragma unroll
-                        for (int k = 1; k < NB; ++k)
-#pragma unroll
-                            for (int ch = 0; ch < 3; ++ch) rgb[ch] = rgb[ch] + bk[k] * sh[3 * k + ch];
-#pragma unroll
-                        for (int ch = 0; ch < 3; ++ch) {
-                            rgb[ch] = rgb[ch] + 0.5f;
-                            if (rgb[ch] < 0.f) clampbits |= (1u << ch);
-                            rgb[ch] = fmaxf(rgb[ch], 0.f);
-                        }
+                        float u[3];
+                        view_dir(cam, p[0], p[1], p[2], u);
+                        clampbits = sh_colour<DEG>(u, sh, rgb);
                     } else {
                         rect = make_int4(0, 0, 0, 0);
                     }
@@ -587,28 +548,17 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_fwd_views_kernel(
             }
             fv.radii[i] = rad;
             fv.depths[i] = depth;
-            float4* r = fv.rec + 6 * (size_t)i;
-            r[0] = make_float4(T.Tu[0], T.Tu[1], T.Tu[2], cxy[0]);
-            r[1] = make_float4(T.Tv[0], T.Tv[1], T.Tv[2], cxy[1]);
-            r[2] = make_float4(T.Tw[0], T.Tw[1], T.Tw[2], opv);
-            r[3] = make_float4(nv[0], nv[1], nv[2], rgb[0]);
-            r[4] = make_float4(rgb[1], rgb[2], lo[0], lo[1]);
-            r[5] = make_float4(hi[0], hi[1], 0.f, 0.f);
+            write_surfel_rec(fv.rec + 6 * (size_t)i, T, cxy, opv, nv, rgb, lo, hi);
             fv.rect[i] = rect;
             fv.tiles[i] = tiles;
             fv.clamped[i] = (uint8_t)clampbits;
         }
-        uint32_t t = tiles;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-        if ((threadIdx.x & 63) == 0) wsum[v][threadIdx.x >> 6] = t;
+        wave_tiles_sum(tiles, wsum[v]);
     }
     __syncthreads();
     if ((int)threadIdx.x < a.V) {
         const SFwdView& fv = a.v[threadIdx.x];
-        const uint32_t bs = wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
-        fv.block_sums[blockIdx.x] = bs;
-        fv.block_offs[blockIdx.x] = bs ? atomicAdd(fv.num_rendered, bs) : 0u;
+        publish_block_sum(wsum[threadIdx.x], fv.block_sums, fv.block_offs, fv.num_rendered);
     }
 }
 
@@ -766,20 +716,9 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_preprocess_bwd_views_kernel(
             ds1 += R[3 * r + 1] * dv[1][r];
         }
         float dscale0 = scale_modifier * ds0, dscale1 = scale_modifier * ds1;
-        const float qr = q.x, qx = q.y, qy = q.z, qz = q.w;
-        float4 drot;
-#define G_(r_, c_) dR[3 * (r_) + (c_)]
-        drot.x = 2.f * (-qz * G_(0, 1) + qy * G_(0, 2) + qz * G_(1, 0) - qx * G_(1, 2) - qy * G_(2, 0) + qx * G_(2, 1));
-        drot.y = 2.f * (qy * G_(0, 1) + qz * G_(0, 2) + qy * G_(1, 0) - 2.f * qx * G_(1, 1) - qr * G_(1, 2) + qz * G_(2, 0) + qr * G_(2, 1) - 2.f * qx * G_(2, 2));
-        drot.z = 2.f * (-2.f * qy * G_(0, 0) + qx * G_(0, 1) + qr * G_(0, 2) + qx * G_(1, 0) + qz * G_(1, 2) - qr * G_(2, 0) + qz * G_(2, 1) - 2.f * qy * G_(2, 2));
-        drot.w = 2.f * (-2.f * qz * G_(0, 0) - qr * G_(0, 1) + qx * G_(0, 2) + qr * G_(1, 0) - 2.f * qz * G_(1, 1) + qy * G_(1, 2) + qx * G_(2, 0) + qy * G_(2, 1));
-#undef G_
-        if (flags & GDR_IN_RAW_SCALES) { dscale0 *= sc0; dscale1 *= sc1; }
-        if (flags & GDR_IN_RAW_ROTATIONS) {
-            const float dot = (q.x * drot.x + q.y * drot.y) + (q.z * drot.z + q.w * drot.w);
-            drot = make_float4((drot.x - q.x * dot) * inv_n, (drot.y - q.y * dot) * inv_n, (drot.z - q.z * dot) * inv_n,
-                               (drot.w - q.w * dot) * inv_n);
-        }
+        float4 drot = quat_grad(q, dR);
+        if (flags & GDR_IN_RAW_SCALES) { dscale0 = act_exp_grad(dscale0, sc0); dscale1 = act_exp_grad(dscale1, sc1); }
+        if (flags & GDR_IN_RAW_ROTATIONS) drot = act_normalize_grad(q, drot, inv_n);
         if (flags & GDR_IN_RAW_OPACITY) { const float o = act_sigmoid(opacities[i]); dop = dop * (o * (1.f - o)); }
         if (accumulate) {
             const float4 om = dL_dmean2D[i];

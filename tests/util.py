@@ -336,3 +336,32 @@ def assert_grads_surfel(hg, g64, g32, keys, what, max_outside=SURFEL_MAX_OUTSIDE
         assert out < max(max_outside, few), (what, k, "(a)", out)
         assert o_h64 <= 1.25 * o_3264 + max(5e-4, few), (what, k, "(b)", o_h64, o_3264)
         assert maxn <= max(2.0, worst_factor) * m_3264 + 1e-4 and m_h64 <= max(worst_factor * m_3264 + 1e-5, 1e-4), (what, k, "(c)", maxn, m_h64, m_3264)
+
+
+# ---- shared by the small-shape multi-view preprocess tests (3DGS and surfel path) --------------------------------------
+SMALL_HW = 64                 # image side
+SMALL_MAX_VIEWS = 8           # GDR_MAX_VIEWS
+
+
+def small_cams(dev=None):
+    from generativedensification_amd.camera import orbit_cameras
+
+    return orbit_cameras(SMALL_MAX_VIEWS, SMALL_HW, SMALL_HW, device=dev) if dev is not None else \
+        orbit_cameras(SMALL_MAX_VIEWS, SMALL_HW, SMALL_HW)
+
+
+def small_hidden_point():
+    """A point that no orbit camera sees: far away, in the direction furthest from every camera's viewing direction."""
+    import math
+
+    eyes = torch.stack([c.camera_center.cpu().float() for c in small_cams()])
+    look = -torch.nn.functional.normalize(eyes, dim=-1)                   # the cameras look at the origin
+    cand = torch.nn.functional.normalize(torch.randn(512, 3, generator=torch.Generator().manual_seed(5)), dim=-1)
+    worst = (cand @ look.T).max(dim=1).values                              # cosine to the nearest viewing direction
+    best = int(worst.argmin())
+    assert float(worst[best]) < math.cos(0.9)                              # the frustum's half-diagonal is 0.51 rad
+    return 100.0 * cand[best]
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
