@@ -183,6 +183,10 @@ GDR_NORM_DTYPES = {"f16": 0, "bf16": 1, "f32": 2}
 GDR_NORM_ROWS, GDR_NORM_MAX_CHANNELS, GDR_NORM_MAX_SEGMENTS, GDR_NORM_MAX_FREQS, GDR_NORM_MAX_UPSCALE = 32, 1024, 1024, 16, 16
 
 
+GDR_GROUPATTN_MAX_HEADS, GDR_GROUPATTN_MAX_QUERIES, GDR_GROUPATTN_MAX_KEYS, GDR_GROUPATTN_MAX_BLOCK = 64, 64, 64, 8
+GDR_GROUPATTN_NORM_ROWS = 64
+
+
 GDR_DENSIFY_MODES = {"top_k": 0, "top_p": 1}
 GDR_DENSIFY_MAX_SEGMENTS, GDR_DENSIFY_MAX_CHANNELS, GDR_DENSIFY_CHUNK = 1024, 1024, 1024
 
@@ -370,6 +374,19 @@ _PROTOS = {
                                        C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "gdr_viewattn_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_groupattn_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_groupattn_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_groupattn_patchify_norm_forward": (C.c_int, [C.c_void_p, C.c_int32] * 3 + [C.c_int64] + [C.c_int32] * 5 +
+                                            [C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_groupattn_norm_unpatchify_forward": (C.c_int, [C.c_void_p, C.c_int32] * 3 + [C.c_int64] + [C.c_int32] * 5 +
+                                              [C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_groupattn_norm_backward_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gdr_groupattn_patchify_norm_backward": (C.c_int, [C.c_void_p, C.c_int32] * 3 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_int32] * 5 +
+                                             [C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_groupattn_norm_unpatchify_backward": (C.c_int, [C.c_void_p, C.c_int32] * 3 + [C.c_int32, C.c_int64] + [C.c_int32] * 5 +
+                                               [C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

@@ -444,14 +444,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_mask_dest_kernel(const uint8_t* _
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-int unsupported(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_UNSUPPORTED;
-}
-
-bool bad_dtype(int32_t dt) { return dt < GDR_NORM_F16 || dt > GDR_NORM_F32; }
 int elem_bytes(int32_t dt) { return dt == GDR_NORM_F32 ? 4 : 2; }
-bool bad_rows(const void* ptr, int64_t stride, int64_t C) { return misaligned(ptr, 15) || stride < C || stride % 8; }
 
 int check_rows(int64_t N, int64_t C) {
     if (N < 0) return invalid_arg("densify: N must be >= 0");

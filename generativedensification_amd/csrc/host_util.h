@@ -19,6 +19,11 @@ static inline int launch_status(const char* what) {
     return GDR_ERR_HIP;
 }
 
+static inline int unsupported(const char* what) {
+    set_error(what, hipSuccess);
+    return GDR_ERR_UNSUPPORTED;
+}
+
 static inline int workspace_too_small(const char* what) {
     set_error(what, hipSuccess);
     return GDR_ERR_WORKSPACE;
@@ -28,5 +33,11 @@ static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a
 
 // mask = alignment in bytes - 1; a NULL pointer is aligned
 static inline bool misaligned(const void* p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
+
+// a storage type code of the row kernels (GDR_NORM_F16 / BF16 / F32)
+static inline bool bad_dtype(int32_t dt) { return dt < GDR_NORM_F16 || dt > GDR_NORM_F32; }
+
+// a (rows, C) matrix read or written in 8-element pieces: 16-byte base, a stride that is a multiple of 8 and at least C
+static inline bool bad_rows(const void* ptr, int64_t stride, int64_t C) { return misaligned(ptr, 15) || stride < C || stride % 8; }
 
 }  // namespace gdr

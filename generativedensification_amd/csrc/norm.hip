@@ -81,30 +81,6 @@ struct AdaP {
     float eps;
 };
 
-// mean and rstd of the row a group holds in x (lanes / pieces that are off hold zeros)
-template <int K>
-__device__ __forceinline__ void row_stats(const float (&x)[K][8], const bool (&on)[K], int lc, float inv_c, float eps, float& mean,
-                                          float& rstd) {
-    // around the row's first value: a constant row then has mean = that value and variance 0 exactly, whatever the value
-    const float pivot = __shfl(x[0][0], (int)(threadIdx.x & (GDR_WAVE - 1)) & ~(lc - 1), GDR_WAVE);
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        if (on[k]) {
-#pragma unroll
-            for (int v = 0; v < 8; ++v) s += x[k][v] - pivot;
-        }
-    mean = pivot + group_sum(s, lc) * inv_c;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        if (on[k]) {
-#pragma unroll
-            for (int v = 0; v < 8; ++v) { const float d = x[k][v] - mean; q += d * d; }
-        }
-    rstd = 1.0f / sqrtf(group_sum(q, lc) * inv_c + eps);
-}
-
 template <int K>
 __global__ __launch_bounds__(NM_BLOCK) void ada_fwd_kernel(const AdaP p) {
     const int tid = threadIdx.x, lc = 1 << p.lc_shift, l = tid & (lc - 1);
@@ -456,14 +432,8 @@ __global__ __launch_bounds__(NM_BLOCK) void pe_bwd_kernel(const PeP p) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-int unsupported(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_UNSUPPORTED;
-}
-
 constexpr int64_t NM_MAX_ROWS = INT64_C(0x7fffffff);
 
-bool bad_dtype(int32_t dt) { return dt < GDR_NORM_F16 || dt > GDR_NORM_F32; }
 int elem_bytes(int32_t dt) { return dt == GDR_NORM_F32 ? 4 : 2; }
 
 // 0, or the status with the message set
@@ -486,9 +456,6 @@ int check_pe(int64_t P, int64_t S, int64_t C, int64_t F) {
     if (P > NM_MAX_ROWS / S) return unsupported("norm_pe: P * S must be below 2^31");
     return check_channels(C);
 }
-
-// a (rows, C) matrix read or written in 8-element pieces: 16-byte base, a stride that is a multiple of 8 and at least C
-bool bad_rows(const void* ptr, int64_t stride, int64_t C) { return misaligned(ptr, 15) || stride < C || stride % 8; }
 
 struct AdaWs { size_t seg, part, bytes; };
 

@@ -1,5 +1,6 @@
-// row_io.h — elements of a runtime storage type (GDR_NORM_F16 / BF16 / F32) <-> f32 on the device, and the lane-group row
-// sum, as norm.hip and densify.hip use them (internal; include after gdr_common.h).
+// row_io.h — elements of a runtime storage type (GDR_NORM_F16 / BF16 / F32) <-> f32 on the device, the lane-group row sum and
+// the LayerNorm statistics of a row held by a lane group, as norm.hip, densify.hip, viewattn.hip and groupattn.hip use them
+// (internal; include after gdr_common.h).
 #pragma once
 #include "half_bits.h"
 
@@ -45,6 +46,30 @@ __device__ __forceinline__ void store1(void* base, int64_t idx, int dt, float x)
 __device__ __forceinline__ float group_sum(float v, int lc) {
     for (int m = lc >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, GDR_WAVE);
     return v;
+}
+
+// mean and rstd of the row a group holds in x (lanes / pieces that are off hold zeros)
+template <int K>
+__device__ __forceinline__ void row_stats(const float (&x)[K][8], const bool (&on)[K], int lc, float inv_c, float eps, float& mean,
+                                          float& rstd) {
+    // around the row's first value: a constant row then has mean = that value and variance 0 exactly, whatever the value
+    const float pivot = __shfl(x[0][0], (int)(threadIdx.x & (GDR_WAVE - 1)) & ~(lc - 1), GDR_WAVE);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (on[k]) {
+#pragma unroll
+            for (int v = 0; v < 8; ++v) s += x[k][v] - pivot;
+        }
+    mean = pivot + group_sum(s, lc) * inv_c;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (on[k]) {
+#pragma unroll
+            for (int v = 0; v < 8; ++v) { const float d = x[k][v] - mean; q += d * d; }
+        }
+    rstd = 1.0f / sqrtf(group_sum(q, lc) * inv_c + eps);
 }
 
 // lanes per row (as a shift, 8..64 lanes) and 8-channel pieces per lane, for C a multiple of 8 in 8..1024

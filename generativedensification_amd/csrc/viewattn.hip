@@ -307,13 +307,6 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_bwd_many_kernel(const VaP p
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-int unsupported(const char* what) {
-    set_error(what, hipSuccess);
-    return GDR_ERR_UNSUPPORTED;
-}
-
-bool bad_dtype(int32_t dt) { return dt < GDR_NORM_F16 || dt > GDR_NORM_F32; }
-bool bad_rows(const void* ptr, int64_t stride, int64_t C) { return misaligned(ptr, 15) || stride < C || stride % 8; }
 
 int check_shape(int64_t N, int32_t H, int32_t Ck, int32_t V, float scale) {
     if (N < 0 || H < 1 || V < 1 || Ck < 1) return invalid_arg("viewattn: N must be >= 0 and H, Ck, V >= 1");

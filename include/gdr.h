@@ -946,6 +946,61 @@ int gdr_viewattn_backward(const void* grad_out, int64_t grad_out_stride, int32_t
                           int32_t t_dtype, const void* cond, int64_t cond_stride, int32_t cond_dtype, int64_t N, int32_t H, int32_t Ck,
                           int32_t V, float scale, void* grad_t, void* grad_cond, void* stream);
 
+/* ---- group cross attention of the volume transformer (csrc/groupattn.hip; added in v17, backward-compatible) ----------------
+ * The core of a multi-head cross attention in which the Lq queries of a group share its Lk keys, and the two LayerNorms that
+ * carry a (B, D, H, W, C) volume into patch order and back (generativedensification_amd/groupattn.py):
+ * s[m, h, i, j] = scale * <q[m, i, h], k[m, j, h]>, p = softmax_j(s), out[m, i, h] = sum_j p[m, h, i, j] * v[m, j, h].  The
+ * arithmetic, its backward and the row map are restated in the header of csrc/groupattn.hip.  The caller owns every buffer;
+ * all are device memory.  Every `*_dtype` is one of GDR_NORM_F16 / BF16 / F32 and the types of one call are independent; the
+ * arithmetic is f32.  Refusals happen before any launch; M = 0 / B = 0 return GDR_OK without a row launch; no entry point
+ * allocates or synchronises with the host.  No atomics: two runs are bitwise equal.
+ * Envelope (GDR_ERR_UNSUPPORTED beyond it): Dh 8, 16 or 32, 1 <= H <= GDR_GROUPATTN_MAX_HEADS, 1 <= Lq <=
+ * GDR_GROUPATTN_MAX_QUERIES, 1 <= Lk <= GDR_GROUPATTN_MAX_KEYS, M <= 2^24; C a multiple of 8 in 8..GDR_NORM_MAX_CHANNELS,
+ * 1 <= bs <= GDR_GROUPATTN_MAX_BLOCK, B D H W below 2^31; and "rows of X": a 16-byte aligned base and a row stride (in
+ * elements) that is a multiple of 8 and >= the row.
+ *
+ * forward: rows of q (M * Lq, H * Dh), k and v (M * Lk, H * Dh), each through its own stride (k and v may be the two halves of
+ *   one (M * Lk, 2 H Dh) matrix); out (M * Lq, H * Dh) dense, 16-byte aligned.  1 launch.
+ * backward: rows of grad_out (M * Lq, H * Dh); q, k, v as in the forward; p is recomputed.  grad_q dense of q_dtype, grad_k /
+ *   grad_v (M * Lk, H * Dh) dense of k_dtype / v_dtype, all 16-byte aligned and written whole.  1 launch.
+ * patchify_norm_forward: vol (B, D, H, W, C) dense (a channels-last volume), D, H, W multiples of bs; patches (B G bs^3, C)
+ *   dense of patches_dtype = the rows of vol in patch order (rounded when patches_dtype is narrower than vol_dtype); normed,
+ *   same shape, of normed_dtype = the LayerNorm over C of the patches as stored.  weight / bias: C values or NULL.  1 launch.
+ * norm_unpatchify_forward: patches (B G bs^3, C) dense; vol (B, D, H, W, C) dense of vol_dtype = the LayerNorm of the rows,
+ *   each at its voxel.  1 launch.
+ * *_backward: grad_vol / grad_patches (the gradient of the input) dense of the input's dtype, written whole; a NULL
+ *   grad_normed / grad_patches input is a zero gradient; grad_weight / grad_bias: C values of weight_dtype / bias_dtype or
+ *   NULL (not wanted).  workspace: gdr_groupattn_norm_backward_bytes(B D H W, C) bytes, 256-byte aligned: one partial pair per
+ *   GDR_GROUPATTN_NORM_ROWS rows.  1 launch for the rows + 1 that folds the partials when a parameter gradient is wanted. */
+#define GDR_GROUPATTN_MAX_HEADS 64
+#define GDR_GROUPATTN_MAX_QUERIES 64
+#define GDR_GROUPATTN_MAX_KEYS 64
+#define GDR_GROUPATTN_MAX_BLOCK 8
+#define GDR_GROUPATTN_NORM_ROWS 64     /* rows per workgroup of the norm backwards */
+int gdr_groupattn_forward(const void* q, int64_t q_stride, int32_t q_dtype, const void* k, int64_t k_stride, int32_t k_dtype,
+                          const void* v, int64_t v_stride, int32_t v_dtype, int64_t M, int32_t Lq, int32_t Lk, int32_t H, int32_t Dh,
+                          float scale, void* out, int32_t out_dtype, void* stream);
+int gdr_groupattn_backward(const void* grad_out, int64_t grad_out_stride, int32_t grad_out_dtype, const void* q, int64_t q_stride,
+                           int32_t q_dtype, const void* k, int64_t k_stride, int32_t k_dtype, const void* v, int64_t v_stride,
+                           int32_t v_dtype, int64_t M, int32_t Lq, int32_t Lk, int32_t H, int32_t Dh, float scale, void* grad_q,
+                           void* grad_k, void* grad_v, void* stream);
+int gdr_groupattn_patchify_norm_forward(const void* vol, int32_t vol_dtype, const void* weight, int32_t weight_dtype, const void* bias,
+                                        int32_t bias_dtype, int64_t B, int32_t D, int32_t H, int32_t W, int32_t C, int32_t bs, float eps,
+                                        void* patches, int32_t patches_dtype, void* normed, int32_t normed_dtype, void* stream);
+int gdr_groupattn_norm_unpatchify_forward(const void* patches, int32_t patches_dtype, const void* weight, int32_t weight_dtype,
+                                          const void* bias, int32_t bias_dtype, int64_t B, int32_t D, int32_t H, int32_t W, int32_t C,
+                                          int32_t bs, float eps, void* vol, int32_t vol_dtype, void* stream);
+size_t gdr_groupattn_norm_backward_bytes(int64_t rows, int32_t C);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_groupattn_patchify_norm_backward(const void* grad_normed, int32_t grad_normed_dtype, const void* grad_patches,
+                                         int32_t grad_patches_dtype, const void* vol, int32_t vol_dtype, int32_t patches_dtype,
+                                         const void* weight, int32_t weight_dtype, int32_t bias_dtype, int64_t B, int32_t D, int32_t H, int32_t W, int32_t C,
+                                         int32_t bs, float eps, void* workspace, size_t workspace_bytes, void* grad_vol, void* grad_weight,
+                                         void* grad_bias, void* stream);
+int gdr_groupattn_norm_unpatchify_backward(const void* grad_vol, int32_t grad_vol_dtype, const void* patches, int32_t patches_dtype,
+                                           const void* weight, int32_t weight_dtype, int32_t bias_dtype, int64_t B, int32_t D, int32_t H,
+                                           int32_t W, int32_t C, int32_t bs, float eps, void* workspace, size_t workspace_bytes,
+                                           void* grad_patches, void* grad_weight, void* grad_bias, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
