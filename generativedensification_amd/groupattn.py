@@ -26,7 +26,8 @@ no rows return empty tensors without loading the library.  Non-finite inputs are
 Outside the core's envelope `grouped_cross_attention` runs F.scaled_dot_product_attention on the same projected tensors and
 warns once.  Under autocast the bound forward keeps the patches, both fused norms' results and its own result in the autocast
 dtype, as the reference's path does through its two einsums, and it hands the convolution an NCDHW copy of the channels-last
-volume because that is the faster convolution (BASELINE §4-groupattn).
+volume because that is the faster of torch's convolutions (BASELINE §4-groupattn).  `CONV_BACKEND = "hip"` hands
+the channels-last volume to conv3d.py's kernels instead; the default "torch" is the path above, bit for bit.
 """
 from __future__ import annotations
 
@@ -37,6 +38,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import _marshal as M
+from . import conv3d as C3
 
 __all__ = ["group_cross_attention", "patchify_layer_norm", "layer_norm_unpatchify", "project_qkv", "grouped_cross_attention",
            "group_att_block_forward", "in_envelope", "MAX_HEADS", "MAX_QUERIES", "MAX_KEYS", "MAX_GROUPS", "HEAD_WIDTHS",
@@ -47,6 +49,11 @@ MAX_GROUPS = 1 << 24
 HEAD_WIDTHS = (8, 16, 32)
 MAX_CHANNELS, MAX_BLOCK = L.GDR_NORM_MAX_CHANNELS, L.GDR_GROUPATTN_MAX_BLOCK
 MAX_ROWS = (1 << 31) - 1
+
+# the convolution at the tail of group_att_block_forward: "torch" = the module's own nn.Conv3d on an NCDHW copy of the volume (the
+# default); "hip" = conv3d.conv3d_of on the channels-last volume itself, the residual added in its epilogue, wherever the module
+# and the shape lie inside that kernel's envelope (INTEGRATION §15 has the measured recommendation per mode)
+CONV_BACKEND = "torch"
 
 _DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
            torch.float32: L.GDR_NORM_DTYPES["f32"]}
@@ -406,6 +413,10 @@ def group_att_block_forward(self, x, cond, group_axis, block_size):
     patches = patches + grouped_cross_attention(self.cross_attn, normed, cond)
     patches = patches + self.mlp(self.norm2(patches))
     vol = layer_norm_unpatchify(patches, x.shape, block_size, self.norm3.weight, self.norm3.bias, self.norm3.eps, out_dtype=cast)
-    # the convolution gets an NCDHW copy: on channels-last input it measured 0.7 ms (fp32) to 6 ms (bf16) slower at the
+    if CONV_BACKEND not in ("torch", "hip"):
+        raise ValueError(f"groupattn.CONV_BACKEND must be 'torch' or 'hip', not {CONV_BACKEND!r}")
+    if CONV_BACKEND == "hip" and C3.covers(self.cnn) and C3.in_envelope(vol.shape[0], self.cnn.in_channels, self.cnn.out_channels, *vol.shape[2:]):
+        return C3.conv3d_of(self.cnn, vol, add_input=True)
+    # torch's convolution gets an NCDHW copy: on channels-last input it measured 0.7 ms (fp32) to 6 ms (bf16) slower at the
     # reference shape, more than this forward saves (BASELINE §4-groupattn); the sum keeps vol's channels-last strides
     return vol + self.cnn(vol.contiguous())

@@ -1001,6 +1001,48 @@ int gdr_groupattn_norm_unpatchify_backward(const void* grad_vol, int32_t grad_vo
                                            int32_t W, int32_t C, int32_t bs, float eps, void* workspace, size_t workspace_bytes,
                                            void* grad_patches, void* grad_weight, void* grad_bias, void* stream);
 
+/* ---- dense 3x3x3 convolution of channels-last volumes (csrc/conv3d.hip; added in v17, backward-compatible) -------------------
+ * The nn.Conv3d(C, C, 3, padding=1) of the volume transformer's blocks on (B, D, H, W, C) rows
+ * (generativedensification_amd/conv3d.py): stride 1, zero padding 1, dilation 1, groups 1, cross-correlation;
+ * out[voxel][co] = bias[co] + addend[voxel][co] + sum over the 27 taps k and ci of x[voxel + offset_k][ci] * weight[co][ci][k],
+ * tap k = (kd * 3 + kh) * 3 + kw, offset_k = (kd, kh, kw) - 1, a voxel outside the volume contributing zero.  The arithmetic
+ * and its gradients are restated in the header of csrc/conv3d.hip.  The caller owns every buffer; all are device memory.
+ * `dtype` (GDR_NORM_F16 / BF16 / F32) is the compute dtype: the type of x, of the packed weight, of the addend and of the
+ * result; sums are f32.  The parameters and their gradients carry dtypes of their own.  Refusals happen before any launch;
+ * B = 0 returns GDR_OK without a product launch; no entry point allocates or synchronises with the host.  No atomics: two
+ * runs are bitwise equal.
+ * Envelope (GDR_ERR_UNSUPPORTED beyond it): Cin and Cout multiples of 8 in 8..GDR_CONV3D_MAX_CHANNELS, B D H W below 2^31, every
+ * row buffer dense and 16-byte aligned, a workspace 256-byte aligned.
+ *
+ * workspace_bytes: the size of one workspace kind for a call of these sizes; no device work; 0: the arguments are refused
+ *   (gdr_last_error).  GDR_CONV3D_WS_PACKED: one packed weight (voxels is not read); GDR_CONV3D_WS_GRAD_WEIGHT: the f32 partial
+ *   tiles of grad_weight, one (27, Cout, Cin) set per voxel slab; GDR_CONV3D_WS_GRAD_BIAS: the column-sum partials (Cin is not read).
+ * pack_weight: weight (Cout, Cin, 3, 3, 3) dense of weight_dtype -> packed, rounded to `dtype`.  mirrored = 0: [k][co][ci], the
+ *   forward's operand; mirrored != 0: [26 - k][ci][co], the operand of the input gradient.  1 launch.
+ * forward: out (B, D, H, W, Cout) from x (B, D, H, W, Cin) and a packed weight (27, Cout, Cin); bias: Cout values of bias_dtype,
+ *   rounded to `dtype`, or NULL; addend: (B, D, H, W, Cout) rows of `dtype` added to the f32 sum before the one rounding, or
+ *   NULL.  The input gradient is this call on grad_out with the mirrored weight and Cin / Cout exchanged.  A workgroup owns a
+ *   brick of GDR_CONV3D_BRICK_D x _H x _W voxels of one batch item.  1 launch.
+ * grad_weight: (Cout, Cin, 3, 3, 3) dense of grad_weight_dtype, written whole, rounded once from the f32 sums.  2 launches.
+ * grad_bias: Cout values of grad_bias_dtype = the column sums of grad_out (voxels, Cout).  2 launches. */
+#define GDR_CONV3D_MAX_CHANNELS 1024
+#define GDR_CONV3D_BRICK_D 4
+#define GDR_CONV3D_BRICK_H 4
+#define GDR_CONV3D_BRICK_W 8
+#define GDR_CONV3D_WS_PACKED 0
+#define GDR_CONV3D_WS_GRAD_WEIGHT 1
+#define GDR_CONV3D_WS_GRAD_BIAS 2
+size_t gdr_conv3d_workspace_bytes(int32_t what, int32_t dtype, int64_t voxels, int32_t Cin, int32_t Cout);
+int gdr_conv3d_pack_weight(const void* weight, int32_t weight_dtype, int32_t Cin, int32_t Cout, int32_t mirrored, void* packed,
+                           int32_t dtype, void* stream);
+int gdr_conv3d_forward(const void* x, int32_t dtype, const void* packed, const void* bias, int32_t bias_dtype, const void* addend,
+                       int64_t B, int32_t D, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* out, void* stream);
+int gdr_conv3d_grad_weight(const void* x, const void* grad_out, int32_t dtype, int64_t B, int32_t D, int32_t H, int32_t W, int32_t Cin,
+                           int32_t Cout, void* workspace, size_t workspace_bytes, void* grad_weight, int32_t grad_weight_dtype,
+                           void* stream);
+int gdr_conv3d_grad_bias(const void* grad_out, int32_t dtype, int64_t voxels, int32_t Cout, void* workspace, size_t workspace_bytes,
+                         void* grad_bias, int32_t grad_bias_dtype, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
