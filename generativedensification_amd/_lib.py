@@ -189,6 +189,10 @@ GDR_GROUPATTN_NORM_ROWS = 64
 GDR_CONV3D_MAX_CHANNELS, GDR_CONV3D_BRICK = 1024, (4, 4, 8)
 GDR_CONV3D_WS_PACKED, GDR_CONV3D_WS_GRAD_WEIGHT, GDR_CONV3D_WS_GRAD_BIAS = 0, 1, 2
 
+GDR_DECONV3D_MAX_CIN, GDR_DECONV3D_MAX_COUT, GDR_DECONV3D_TILE_ROWS, GDR_DECONV3D_SLAB_MIN = 1024, 256, 64, 4096
+(GDR_DECONV3D_WS_PACKED, GDR_DECONV3D_WS_GRAD_WEIGHT, GDR_DECONV3D_WS_GRAD_BIAS, GDR_DECONV3D_WS_GRAD_INPUT,
+ GDR_DECONV3D_WS_STATS) = 0, 1, 2, 3, 4
+
 
 GDR_DENSIFY_MODES = {"top_k": 0, "top_p": 1}
 GDR_DENSIFY_MAX_SEGMENTS, GDR_DENSIFY_MAX_CHANNELS, GDR_DENSIFY_CHUNK = 1024, 1024, 1024
@@ -398,6 +402,16 @@ _PROTOS = {
                                [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p]),
     "gdr_conv3d_grad_bias": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
                                        C.c_void_p]),
+    "gdr_deconv3d_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "gdr_deconv3d_pack_weight": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_deconv3d_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_int32, C.c_double, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 3),
+    "gdr_deconv3d_grad_input": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64] +
+                                [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_deconv3d_grad_weight": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_int64] + [C.c_int32] * 5 + [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_deconv3d_grad_bias": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32,
+                                         C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

@@ -1043,6 +1043,61 @@ int gdr_conv3d_grad_weight(const void* x, const void* grad_out, int32_t dtype, i
 int gdr_conv3d_grad_bias(const void* grad_out, int32_t dtype, int64_t voxels, int32_t Cout, void* workspace, size_t workspace_bytes,
                          void* grad_bias, int32_t grad_bias_dtype, void* stream);
 
+/* ---- [LayerNorm +] 2x transposed convolution of channels-last volumes (csrc/deconv3d.hip; entry points added within v17) -----
+ * The nn.LayerNorm(Cin) and nn.ConvTranspose3d(Cin, Cout, kernel_size=2, stride=2) at the tail of the volume transformer
+ * (generativedensification_amd/deconv3d.py) on (B, D, H, W, Cin) rows:
+ * out[(b, 2d + i, 2h + j, 2w + k)][co] = bias[co] + sum over ci of n[(b, d, h, w)][ci] * weight[ci][co][t], tap t = (i * 2 + j) * 2 + k,
+ * n = x, or with has_norm the row's LayerNorm (biased variance, eps inside the root, optional affine) computed in the same
+ * kernel and rounded once to the compute dtype (f32 rows: not rounded at all).  The arithmetic and its gradients are restated
+ * in the header of csrc/deconv3d.hip.  The caller owns every buffer; all are device memory.  `dtype` (GDR_NORM_F16 / BF16 /
+ * F32) is the compute dtype: the type of x, of the packed weight, of grad_out and of the results; sums are f32 (f64 for f32
+ * rows).  The parameters and their gradients carry dtypes of their own; the LayerNorm's affine parameters are read as they
+ * are, weight and bias rounded to `dtype`.  Refusals happen before any launch; B = 0 returns GDR_OK; no entry point allocates
+ * or synchronises with the host.  No atomics: two runs are bitwise equal.
+ * Envelope (GDR_ERR_UNSUPPORTED beyond it): Cin a multiple of 8 in 8..GDR_DECONV3D_MAX_CIN, Cout one in
+ * 8..GDR_DECONV3D_MAX_COUT, 8 B D H W (the child rows) below 2^31, every row buffer dense and 16-byte aligned, a workspace
+ * 256-byte aligned.
+ *
+ * workspace_bytes: the size of one workspace kind for `rows` = B D H W parent rows; no device work; 0: the arguments are
+ *   refused (gdr_last_error).  _WS_PACKED: one packed weight (rows is not read); _WS_GRAD_WEIGHT: the partial tiles of
+ *   grad_weight, one (8, Cin, Cout) set per slab of parent rows (a slab is cut per GDR_DECONV3D_SLAB_MIN rows, 8 at most);
+ *   _WS_GRAD_BIAS: the column-sum partials of grad_out; _WS_GRAD_INPUT: the per-workgroup column sums behind grad_ln_weight /
+ *   grad_ln_bias; _WS_STATS: the (rows, 2) f64 mean and rstd the forward leaves for the backward.
+ * pack_weight: weight (Cin, Cout, 2, 2, 2) dense of weight_dtype -> packed, rounded to `dtype`.  transposed = 0: [t][co][ci], the
+ *   forward's operand; transposed != 0: [t][ci][co], the operand of grad_input.  1 launch.
+ * forward: out (B, 2D, 2H, 2W, Cout).  stats: NULL, or with has_norm a _WS_STATS buffer that receives mean and rstd.  A
+ *   workgroup owns GDR_DECONV3D_TILE_ROWS consecutive parent rows.  1 launch.
+ * grad_input: grad_x (B, D, H, W, Cin) (or NULL) from grad_out and the transposed packed weight, with has_norm through the
+ *   LayerNorm's backward (x and the forward's stats are read); grad_ln_weight / grad_ln_bias: Cin values each, or NULL; the
+ *   workspace is read only for them.  1 launch, + 1 for the two sums.
+ * grad_weight: (Cin, Cout, 2, 2, 2) dense of grad_weight_dtype, written whole, rounded once.  2 launches.
+ * grad_bias: Cout values of grad_bias_dtype = the column sums of grad_out (child_rows = 8 B D H W, Cout).  2 launches. */
+#define GDR_DECONV3D_MAX_CIN 1024
+#define GDR_DECONV3D_MAX_COUT 256
+#define GDR_DECONV3D_TILE_ROWS 64
+#define GDR_DECONV3D_SLAB_MIN 4096
+#define GDR_DECONV3D_WS_PACKED 0
+#define GDR_DECONV3D_WS_GRAD_WEIGHT 1
+#define GDR_DECONV3D_WS_GRAD_BIAS 2
+#define GDR_DECONV3D_WS_GRAD_INPUT 3
+#define GDR_DECONV3D_WS_STATS 4
+size_t gdr_deconv3d_workspace_bytes(int32_t what, int32_t dtype, int64_t rows, int32_t Cin, int32_t Cout);
+int gdr_deconv3d_pack_weight(const void* weight, int32_t weight_dtype, int32_t Cin, int32_t Cout, int32_t transposed, void* packed,
+                             int32_t dtype, void* stream);
+int gdr_deconv3d_forward(const void* x, int32_t dtype, const void* packed, const void* bias, int32_t bias_dtype, int32_t has_norm,
+                         const void* ln_weight, int32_t ln_weight_dtype, const void* ln_bias, int32_t ln_bias_dtype, double eps, int64_t B,
+                         int32_t D, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* stats, void* out, void* stream);
+int gdr_deconv3d_grad_input(const void* grad_out, int32_t dtype, const void* packed_t, const void* x, const void* stats, int32_t has_norm,
+                            const void* ln_weight, int32_t ln_weight_dtype, int64_t B, int32_t D, int32_t H, int32_t W, int32_t Cin,
+                            int32_t Cout, void* workspace, size_t workspace_bytes, void* grad_x, void* grad_ln_weight,
+                            int32_t grad_ln_weight_dtype, void* grad_ln_bias, int32_t grad_ln_bias_dtype, void* stream);
+int gdr_deconv3d_grad_weight(const void* x, const void* stats, int32_t has_norm, const void* ln_weight, int32_t ln_weight_dtype,
+                             const void* ln_bias, int32_t ln_bias_dtype, const void* grad_out, int32_t dtype, int64_t B, int32_t D, int32_t H,
+                             int32_t W, int32_t Cin, int32_t Cout, void* workspace, size_t workspace_bytes, void* grad_weight,
+                             int32_t grad_weight_dtype, void* stream);
+int gdr_deconv3d_grad_bias(const void* grad_out, int32_t dtype, int64_t child_rows, int32_t Cout, void* workspace, size_t workspace_bytes,
+                           void* grad_bias, int32_t grad_bias_dtype, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
