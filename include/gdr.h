@@ -1098,6 +1098,57 @@ int gdr_deconv3d_grad_weight(const void* x, const void* stats, int32_t has_norm,
 int gdr_deconv3d_grad_bias(const void* grad_out, int32_t dtype, int64_t child_rows, int32_t Cout, void* workspace, size_t workspace_bytes,
                            void* grad_bias, int32_t grad_bias_dtype, void* stream);
 
+/* ---- coarse Gaussian head (csrc/coarsehead.hip; entry points added within v17) ------------------------------------------------
+ * Decoder.forward_coarse of the reference and the centres / mask lines behind it (generativedensification_amd/coarsehead.py) on
+ * dense (rows, C) rows: Linear(C, C), ReLU, Linear(C, C), ReLU, Linear(C, K P) with P = 3 + sh_dim + 1 + 3 + 4, the split into
+ * offset = 2 sigmoid - 1 (3), sh (sh_dim), opacity + opacity_shift (1), scaling + scaling_shift (3), rotation (4) per k, and
+ * optionally centers = group_centers[row % N] + offset half_cell and mask = sigmoid(opacity) > threshold, in one launch.  The
+ * arithmetic and its gradients are restated in the header of csrc/coarsehead.hip.  `dtype` (GDR_NORM_F16 / BF16 / F32) is the
+ * compute dtype: the type of x, of the packed weights and of grad_x; the hidden rows are rounded to it, sums are f32 (f64 for
+ * f32 rows); the five outputs, centers and every upstream gradient are dense f32 with E = rows K elements: offset (E, 3),
+ * sh (E, sh_dim), scaling (E, 3), rotation (E, 4), opacity (E), centers (E, 3); mask is E bytes of 0 / 1.  Weights are
+ * nn.Linear's (out, in), biases and parameter gradients carry dtypes of their own.  The caller owns every buffer; all are
+ * device memory.  Refusals happen before any launch; rows = 0 returns GDR_OK; no entry point allocates or synchronises with the
+ * host.  No atomics: two runs are bitwise equal.
+ * Envelope (GDR_ERR_UNSUPPORTED beyond it): C a multiple of 8 in 8..GDR_COARSEHEAD_MAX_C (both hidden widths are C), K in 1..4,
+ * sh_dim one of 3, 12, 27, 48, K P <= GDR_COARSEHEAD_MAX_OUT, rows K below 2^31, x / grad_x / packed 16-byte aligned, a
+ * workspace 256-byte aligned.
+ *
+ * workspace_bytes: the size of one workspace kind; no device work; 0: the arguments are refused (gdr_last_error).
+ *   _WS_PACKED_FORWARD / _WS_PACKED_BACKWARD: the packed weights of the forward / the backward (rows is not read);
+ *   _WS_PARTIALS: the partial parameter gradients, one set per slab of rows (a slab is cut per GDR_COARSEHEAD_SLAB_MIN rows,
+ *   1024 at most).
+ * pack: the three weights rounded to `dtype`, zero-padded; backward = 0: the forward's operands, != 0: the backward's.  1 launch.
+ * forward: a workgroup owns GDR_COARSEHEAD_TILE_ROWS consecutive rows.  centers (with group_centers (N, 3) f32, N dividing
+ *   rows) and mask may each be NULL.  1 launch.
+ * backward: recomputes the hidden rows from x; `offset` is the forward's output; any upstream gradient may be NULL (zeros).
+ *   grad_x: (rows, C) of `dtype`, or NULL.  workspace: a _WS_PARTIALS buffer that receives the partial parameter gradients,
+ *   or NULL when no parameter gradient is needed.  1 launch.
+ * fold: the six parameter gradients (any may be NULL) from the partials, added in a fixed order (16 segments of the slabs, each in slab
+ *   order, then the segment sums), each rounded once.  1 launch. */
+#define GDR_COARSEHEAD_MAX_C 256
+#define GDR_COARSEHEAD_MAX_OUT 128
+#define GDR_COARSEHEAD_TILE_ROWS 64
+#define GDR_COARSEHEAD_SLAB_MIN 1024
+#define GDR_COARSEHEAD_WS_PACKED_FORWARD 0
+#define GDR_COARSEHEAD_WS_PACKED_BACKWARD 1
+#define GDR_COARSEHEAD_WS_PARTIALS 2
+size_t gdr_coarsehead_workspace_bytes(int32_t what, int32_t dtype, int64_t rows, int32_t C, int32_t K, int32_t sh_dim);
+int gdr_coarsehead_pack(const void* w1, int32_t w1_dtype, const void* w2, int32_t w2_dtype, const void* w3, int32_t w3_dtype, int32_t C,
+                        int32_t K, int32_t sh_dim, int32_t backward, void* packed, int32_t dtype, void* stream);
+int gdr_coarsehead_forward(const void* x, int32_t dtype, const void* packed, const void* b1, int32_t b1_dtype, const void* b2, int32_t b2_dtype,
+                           const void* b3, int32_t b3_dtype, int64_t rows, int64_t N, int32_t C, int32_t K, int32_t sh_dim,
+                           double opacity_shift, double scaling_shift, const void* group_centers, double half_cell, double threshold,
+                           void* offset, void* sh, void* scaling, void* rotation, void* opacity, void* centers, void* mask, void* stream);
+int gdr_coarsehead_backward(const void* x, int32_t dtype, const void* packed, const void* b1, int32_t b1_dtype, const void* b2, int32_t b2_dtype,
+                            int64_t rows, int32_t C, int32_t K, int32_t sh_dim, const void* offset, const void* grad_offset, const void* grad_sh,
+                            const void* grad_scaling, const void* grad_rotation, const void* grad_opacity, const void* grad_centers,
+                            double half_cell, void* grad_x, void* workspace, size_t workspace_bytes, void* stream);
+int gdr_coarsehead_fold(const void* workspace, size_t workspace_bytes, int32_t dtype, int64_t rows, int32_t C, int32_t K, int32_t sh_dim,
+                        void* grad_w1, int32_t grad_w1_dtype, void* grad_b1, int32_t grad_b1_dtype, void* grad_w2, int32_t grad_w2_dtype,
+                        void* grad_b2, int32_t grad_b2_dtype, void* grad_w3, int32_t grad_w3_dtype, void* grad_b3, int32_t grad_b3_dtype,
+                        void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
