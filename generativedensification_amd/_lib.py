@@ -196,6 +196,9 @@ GDR_DECONV3D_MAX_CIN, GDR_DECONV3D_MAX_COUT, GDR_DECONV3D_TILE_ROWS, GDR_DECONV3
 GDR_COARSEHEAD_MAX_C, GDR_COARSEHEAD_MAX_OUT, GDR_COARSEHEAD_TILE_ROWS, GDR_COARSEHEAD_SLAB_MIN = 256, 128, 64, 1024
 GDR_COARSEHEAD_WS_PACKED_FORWARD, GDR_COARSEHEAD_WS_PACKED_BACKWARD, GDR_COARSEHEAD_WS_PARTIALS = 0, 1, 2
 
+GDR_FINEHEAD_MAX_C, GDR_FINEHEAD_TILE_ROWS, GDR_FINEHEAD_SLAB_MIN, GDR_FINEHEAD_MAX_LEVELS, GDR_FINEHEAD_SCAN_CHUNK = 256, 64, 512, 8, 1024
+GDR_FINEHEAD_WS_PACKED_FORWARD, GDR_FINEHEAD_WS_PACKED_BACKWARD, GDR_FINEHEAD_WS_PARTIALS = 0, 1, 2
+
 
 GDR_DENSIFY_MODES = {"top_k": 0, "top_p": 1}
 GDR_DENSIFY_MAX_SEGMENTS, GDR_DENSIFY_MAX_CHANNELS, GDR_DENSIFY_CHUNK = 1024, 1024, 1024
@@ -423,6 +426,21 @@ _PROTOS = {
                                 [C.c_void_p] * 7 + [C.c_double, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gdr_coarsehead_fold": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32] * 6 +
                             [C.c_void_p]),
+    "gdr_finehead_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "gdr_finehead_backward_step": (C.c_int32, [C.c_int32] * 3),
+    "gdr_finehead_pack": (C.c_int, [C.c_void_p, C.c_int32] * 2 + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_finehead_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_void_p, C.c_int32] * 2 + [C.c_int64, C.c_int32, C.c_int32,
+                                                                                                         C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_finehead_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gdr_finehead_fold": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p, C.c_int32] * 4 +
+                          [C.c_void_p]),
+    "gdr_finehead_scan_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gdr_finehead_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6),
+    "gdr_finehead_assemble": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 +
+                              [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double] + [C.c_void_p] * 6),
+    "gdr_finehead_assemble_backward": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int64] * 3 +
+                                       [C.c_void_p] * 8),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

@@ -1149,6 +1149,82 @@ int gdr_coarsehead_fold(const void* workspace, size_t workspace_bytes, int32_t d
                         void* grad_b2, int32_t grad_b2_dtype, void* grad_w3, int32_t grad_w3_dtype, void* grad_b3, int32_t grad_b3_dtype,
                         void* stream);
 
+/* ---- fine Gaussian head and fine-set assembly (csrc/finehead.hip; entry points added within v17) -------------------------------
+ * The head: `feat2attr` of the reference's GaussianModule / GaussianResModule (generativedensification_amd/finehead.py) on dense
+ * (rows, C) rows: Linear(C, C), GELU (exact, erf), Linear(C, P) with P = sh_dim + 1 + 3 + 4.  `dtype` (GDR_NORM_F16 / BF16 / F32)
+ * is the compute dtype: the type of x, of the packed weights and of grad_x; z1 and the hidden row are rounded to it, GELU and its
+ * derivative are evaluated in f32 (f64 for f32 rows) from the rounded z1, sums are f32 (f64 for f32 rows).  out is (rows, P) dense
+ * of out_dtype, the compute dtype or GDR_NORM_F32 (the last layer's sum without a 16-bit rounding); grad_out is (rows, P) dense of
+ * grad_out_dtype or NULL (zeros).  Weights are nn.Linear's (out, in); biases and parameter gradients carry dtypes of their own.
+ * The caller owns every buffer; all are device memory.  Refusals happen before any launch; rows = 0 returns GDR_OK; no entry
+ * point allocates or synchronises with the host.  No atomics: two runs are bitwise equal.  The arithmetic is restated in the
+ * header of csrc/finehead.hip.
+ * Envelope (GDR_ERR_UNSUPPORTED beyond it): C a multiple of 8 in 8..GDR_FINEHEAD_MAX_C (the hidden width is C), sh_dim one of 3,
+ * 12, 27, 48, rows below 2^31, x / grad_x / packed 16-byte aligned, a workspace 256-byte aligned.
+ *
+ * workspace_bytes: the size of one workspace kind; no device work; 0: the arguments are refused (gdr_last_error).
+ *   _WS_PACKED_FORWARD / _WS_PACKED_BACKWARD: the packed weights of the forward / the backward (rows is not read);
+ *   _WS_PARTIALS: the partial parameter gradients, one set per slab of rows (a slab is cut per GDR_FINEHEAD_SLAB_MIN rows, 256 at
+ *   most).
+ * backward_step: the rows a workgroup of the backward takes per step for this shape (64, 32 or 16; 0: refused).
+ * pack: both weights rounded to `dtype`, zero-padded; backward = 0: the forward's operands, != 0: the backward's.  1 launch.
+ * forward: a workgroup owns GDR_FINEHEAD_TILE_ROWS consecutive rows; the hidden row stays in LDS.  1 launch.
+ * backward: recomputes z1 and the hidden row from x.  grad_x: (rows, C) of `dtype`, or NULL.  workspace: a _WS_PARTIALS buffer
+ *   that receives the partial parameter gradients, or NULL when no parameter gradient is needed.  1 launch.
+ * fold: the four parameter gradients (any may be NULL) from the partials, added in a fixed order (16 segments of the slabs, each
+ *   in slab order, then the segment sums), each rounded once.  1 launch.
+ *
+ * The assembly: the fine Gaussian set of the reference's Network.forward for one sample: the rows of up to
+ * GDR_FINEHEAD_MAX_LEVELS decoder levels, then the coarse Gaussians with mask[i] != 0 whose masked row m has selected[m] == 0 (the
+ * survivors), in row order.  Outputs, dense f32: centers (T, 3), shs (T, sh_dim), opacity (T, 1), scaling (T, 3), rotation (T, 4)
+ * with T = sum of level_rows + n_rest.  A level row gives centers = coord (f32) and, from its attribute row (attr_dtype, P wide,
+ * converted to f32 first), shs = the first sh_dim columns, opacity = the next + opacity_shift, scaling = the next 3 +
+ * scaling_shift, rotation = the last 4.  A survivor row copies the coarse tensors ((Nc, 3 | 1 | 3 | 4) f32) and shs_fine
+ * ((n_masked, sh_dim) f32).  Row counts are below 2^31.
+ * scan: rank_masked (Nc) = the number of masked rows before row i, -1 where mask[i] == 0; row_of_masked (n_masked) its inverse;
+ *   rank_rest (n_masked) = the number of unselected rows before masked row m, -1 where selected; masked_of_rest (n_masked) its
+ *   inverse; count[0] = the masked rows, count[1] = the unselected rows.  Inverse entries nothing maps to are left as they were.
+ *   workspace: gdr_finehead_scan_bytes bytes, 256-byte aligned.  3 launches.
+ * assemble: n_rest (<= n_masked) survivor rows are written; a survivor whose rank is not below n_rest is dropped, a survivor row
+ *   nothing maps to is unspecified, nothing is written outside the T rows.  16-byte stores when every output starts on 16
+ *   bytes.  1 launch.
+ * assemble_backward: upstream gradients (T, w) f32, any may be NULL (zeros).  grad_coord[l] (n_l, 3) f32 and grad_attr[l]
+ *   (n_l, P) of attr_dtype, the dense coarse gradients (a row is its survivor's upstream row or zero) and grad_shs_fine
+ *   (n_masked, sh_dim); any may be NULL (not wanted).  1 launch. */
+#define GDR_FINEHEAD_MAX_C 256
+#define GDR_FINEHEAD_TILE_ROWS 64
+#define GDR_FINEHEAD_SLAB_MIN 512
+#define GDR_FINEHEAD_MAX_LEVELS 8
+#define GDR_FINEHEAD_SCAN_CHUNK 1024      /* rows per workgroup of the scan */
+#define GDR_FINEHEAD_WS_PACKED_FORWARD 0
+#define GDR_FINEHEAD_WS_PACKED_BACKWARD 1
+#define GDR_FINEHEAD_WS_PARTIALS 2
+size_t gdr_finehead_workspace_bytes(int32_t what, int32_t dtype, int64_t rows, int32_t C, int32_t sh_dim);
+int32_t gdr_finehead_backward_step(int32_t dtype, int32_t C, int32_t sh_dim);
+int gdr_finehead_pack(const void* w1, int32_t w1_dtype, const void* w2, int32_t w2_dtype, int32_t C, int32_t sh_dim, int32_t backward,
+                      void* packed, int32_t dtype, void* stream);
+int gdr_finehead_forward(const void* x, int32_t dtype, const void* packed, const void* b1, int32_t b1_dtype, const void* b2, int32_t b2_dtype,
+                         int64_t rows, int32_t C, int32_t sh_dim, void* out, int32_t out_dtype, void* stream);
+int gdr_finehead_backward(const void* x, int32_t dtype, const void* packed, const void* b1, int32_t b1_dtype, int64_t rows, int32_t C,
+                          int32_t sh_dim, const void* grad_out, int32_t grad_out_dtype, void* grad_x, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int gdr_finehead_fold(const void* workspace, size_t workspace_bytes, int32_t dtype, int64_t rows, int32_t C, int32_t sh_dim, void* grad_w1,
+                      int32_t grad_w1_dtype, void* grad_b1, int32_t grad_b1_dtype, void* grad_w2, int32_t grad_w2_dtype, void* grad_b2,
+                      int32_t grad_b2_dtype, void* stream);
+size_t gdr_finehead_scan_bytes(int64_t Nc, int64_t n_masked);      /* 0: the arguments are refused (gdr_last_error) */
+int gdr_finehead_scan(const uint8_t* mask, int64_t Nc, const uint8_t* selected, int64_t n_masked, void* workspace, size_t workspace_bytes,
+                      int32_t* rank_masked, int32_t* row_of_masked, int32_t* rank_rest, int32_t* masked_of_rest, int64_t* count, void* stream);
+int gdr_finehead_assemble(int32_t n_levels, const void* const* coord, const void* const* attr, const int64_t* level_rows, int32_t attr_dtype,
+                          int32_t sh_dim, const void* centers_coarse, const void* opacity_coarse, const void* scaling_coarse,
+                          const void* rotation_coarse, int64_t Nc, const void* shs_fine, int64_t n_masked, const int32_t* row_of_masked,
+                          const int32_t* masked_of_rest, int64_t n_rest, double opacity_shift, double scaling_shift, void* centers, void* shs,
+                          void* opacity, void* scaling, void* rotation, void* stream);
+int gdr_finehead_assemble_backward(int32_t n_levels, const int64_t* level_rows, int32_t attr_dtype, int32_t sh_dim, const void* grad_centers,
+                                   const void* grad_shs, const void* grad_opacity, const void* grad_scaling, const void* grad_rotation,
+                                   const int32_t* rank_masked, const int32_t* rank_rest, int64_t Nc, int64_t n_masked, int64_t n_rest,
+                                   void* const* grad_coord, void* const* grad_attr, void* grad_centers_coarse, void* grad_opacity_coarse,
+                                   void* grad_scaling_coarse, void* grad_rotation_coarse, void* grad_shs_fine, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
