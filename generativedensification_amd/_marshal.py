@@ -38,3 +38,26 @@ def workspace(nbytes: int, dev):
     """A uint8 workspace of `nbytes` on `dev` as (tensor, base, usable bytes); keep the tensor alive through the call."""
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     return (ws, *aligned_base(ws.data_ptr(), nbytes))
+
+
+def f32_contiguous(name, t, shape, dev=None):
+    """`t` as the kernels read it: a float32 tensor of `shape` (None = any extent) on `dev`, contiguous.  Shapes are
+    refused with a ValueError, other dtypes and devices with a TypeError / RuntimeError, before any launch."""
+    if not isinstance(t, torch.Tensor) or t.dim() != len(shape) or any(w is not None and s != w for s, w in zip(t.shape, shape)):
+        want = "(" + ", ".join("*" if w is None else str(w) for w in shape) + ")"
+        raise ValueError(f"{name} must be a {want} tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, not {t.dtype}")
+    if dev is not None and t.device != dev:
+        raise RuntimeError(f"{name} is on {t.device}, the other tensors on {dev}")
+    return t.contiguous()
+
+
+def rays_and_view(rays, viewmatrix, H, W, dev):
+    """rays (H,W,6) and the 4x4 view matrix as float32 contiguous tensors on `dev` (cameras keep them in any float type and
+    on any device, so these two are converted, not refused)."""
+    if not isinstance(rays, torch.Tensor) or tuple(rays.shape) != (H, W, 6):
+        raise ValueError(f"rays must be a ({H}, {W}, 6) tensor, got {tuple(getattr(rays, 'shape', ()))}")
+    if not isinstance(viewmatrix, torch.Tensor) or tuple(viewmatrix.shape) != (4, 4):
+        raise ValueError(f"viewmatrix must be a (4, 4) tensor, got {tuple(getattr(viewmatrix, 'shape', ()))}")
+    return (rays.to(device=dev, dtype=torch.float32).contiguous(), viewmatrix.to(device=dev, dtype=torch.float32).contiguous())

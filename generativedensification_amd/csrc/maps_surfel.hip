@@ -213,8 +213,36 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_loss_fwd_kernel(Maps m, cons
     if (threadIdx.x == 0) atomicAdd(loss, (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
 }
 
-// pass A: as surfel_maps_bwd_a with g_depth_normal = -(w_normal/P) acc rend_normal go; also keeps the pixel's
-// depth_normal (3 more floats) for pass B's rend_normal gradient
+// The loss's gradient of rend_normal, -(w_normal/P) acc R^T depth_normal, is a three-term rotation that can cancel to a few
+// per cent of its terms, so an ulp on each component of an f32 unit normal becomes tens of ulps of the result (seen at the
+// single interior pixel of a 3x3 image: 23 ulps).  The pixel's normal is therefore formed in double for that gradient: the
+// same reads as stencil_at, the same f32 test for a non-finite quotient, double arithmetic from there on.  Only where the f32
+// stencil is ordinary (1e-12 < |c| < inf): where it overflows (a neighbour at -FLT_MAX), goes NaN or falls under the
+// normalisation's eps, the forward loss and torch see the f32 value, and the gradient keeps to it.
+__device__ __forceinline__ void point_at_d(const Maps& m, int q, size_t P, double* p) {
+    const float D = m.allmap[q], a = m.allmap[P + q], med = m.allmap[5 * P + q];
+    const float e = D / a;
+    const bool eo = !(e != e) && e != INFINITY && e != -INFINITY;
+    const double ed = eo ? (double)D / (double)a : (double)nan0(e);
+    const double sd = (1.0 - (double)m.r) * ed + (double)m.r * (double)nan0(med);
+    const float* ry = m.rays + 6 * (size_t)q;
+    p[0] = fma(sd, (double)ry[3], (double)ry[0]); p[1] = fma(sd, (double)ry[4], (double)ry[1]); p[2] = fma(sd, (double)ry[5], (double)ry[2]);
+}
+
+// depth_normal of interior pixel (y, x) in double: normalize(a x b, eps = 1e-12) times alpha
+__device__ __forceinline__ void depth_normal_d(const Maps& m, int y, int x, size_t P, double alpha, double* dn) {
+    double u[3], d[3], l[3], r[3], a[3], b[3];
+    point_at_d(m, (y - 1) * m.W + x, P, u); point_at_d(m, (y + 1) * m.W + x, P, d);
+    point_at_d(m, y * m.W + x - 1, P, l); point_at_d(m, y * m.W + x + 1, P, r);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { a[k] = d[k] - u[k]; b[k] = r[k] - l[k]; }
+    const double c[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+    const double inv = alpha / fmax(sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), 1e-12);
+    dn[0] = c[0] * inv; dn[1] = c[1] * inv; dn[2] = c[2] * inv;
+}
+
+// pass A: as surfel_maps_bwd_a with g_depth_normal = -(w_normal/P) acc rend_normal go; also writes the pixel's rend_normal
+// gradient (3 more floats), which pass B copies into dL_dallmap[2:5]
 __global__ __launch_bounds__(GDR_BLOCK) void surfel_loss_bwd_a_kernel(Maps m, const float* __restrict__ view, LossW w,
                                                                        const float* __restrict__ go_ptr,
                                                                        float* __restrict__ scratch) {
@@ -223,19 +251,31 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_loss_bwd_a_kernel(Maps m, co
     if (q >= (int)P) return;
     const int y = q / m.W, x = q - y * m.W;
     const float go = go_ptr ? *go_ptr : 1.f;
-    float ga[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f}, dn[3] = {0.f, 0.f, 0.f};
+    float ga[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f}, grn[3] = {0.f, 0.f, 0.f};
     if (y >= 1 && y < m.H - 1 && x >= 1 && x < m.W - 1) {
         Stencil s;
         stencil_at(m, y, x, P, s);
         const float a = m.allmap[P + q];
+        // d/d rend_normal = -(w_normal/P) acc R^T depth_normal
+        if (s.len > 1e-12f && s.len < INFINITY) {
+            double dn[3];
+            depth_normal_d(m, y, x, P, (double)a, dn);
+            const double kn = -((double)w.normal * (double)go / (double)P) * (double)a;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                grn[i] = (float)(kn * ((double)view[i] * dn[0] + (double)view[4 + i] * dn[1] + (double)view[8 + i] * dn[2]));
+        } else {
+            const float il = a / fmaxf(s.len, 1e-12f), kn = -w.normal * (go / (float)P) * a;
+            const float d0 = s.c[0] * il, d1 = s.c[1] * il, d2 = s.c[2] * il;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) grn[i] = kn * fmaf(view[i], d0, fmaf(view[4 + i], d1, view[8 + i] * d2));
+        }
         const float n0 = m.allmap[2 * P + q], n1 = m.allmap[3 * P + q], n2 = m.allmap[4 * P + q];
         const float k = -(w.normal / (float)P) * a * a * go;  // upstream of the UNIT normal: g_dn * alpha
         float g[3], gc[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) g[j] = k * fmaf(view[4 * j], n0, fmaf(view[4 * j + 1], n1, view[4 * j + 2] * n2));
         const float invl = 1.f / fmaxf(s.len, 1e-12f);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) dn[j] = s.c[j] * invl * a;
         if (s.len > 1e-12f) {
             const float nn[3] = {s.c[0] * invl, s.c[1] * invl, s.c[2] * invl};
             const float dot = fmaf(nn[0], g[0], fmaf(nn[1], g[1], nn[2] * g[2]));
@@ -250,7 +290,7 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_loss_bwd_a_kernel(Maps m, co
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        scratch[(size_t)k * P + q] = ga[k]; scratch[(size_t)(3 + k) * P + q] = gb[k]; scratch[(size_t)(6 + k) * P + q] = dn[k];
+        scratch[(size_t)k * P + q] = ga[k]; scratch[(size_t)(3 + k) * P + q] = gb[k]; scratch[(size_t)(6 + k) * P + q] = grn[k];
     }
 }
 
@@ -296,10 +336,8 @@ __global__ __launch_bounds__(GDR_BLOCK) void surfel_loss_bwd_b_kernel(Maps m, co
     const float ge = eo ? (1.f - m.r) * gsd : 0.f;
     dL_dallmap[q] = (eo && a != 0.f) ? ge / a : 0.f;
     dL_dallmap[P + q] = ((eo && a != 0.f) ? -ge * D / (a * a) : 0.f) + w.alpha * invp;  // acc is detached in the normal term
-    const float kn = -w.normal * invp * a;  // d/d rend_normal = -(w_normal/P) acc depth_normal
-    const float d0 = scratch[(size_t)6 * P + q], d1 = scratch[(size_t)7 * P + q], d2 = scratch[(size_t)8 * P + q];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) dL_dallmap[(2 + i) * P + q] = kn * fmaf(view[i], d0, fmaf(view[4 + i], d1, view[8 + i] * d2));
+    for (int i = 0; i < 3; ++i) dL_dallmap[(2 + i) * P + q] = scratch[(size_t)(6 + i) * P + q];  // formed in pass A
     dL_dallmap[5 * P + q] = mo ? m.r * gsd : 0.f;
     dL_dallmap[6 * P + q] = w.dist * invp;
 }

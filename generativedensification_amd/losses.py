@@ -15,8 +15,10 @@ class _ViewLoss(torch.autograd.Function):
     def forward(ctx, color, depth, alpha, target_chw, w_depth, w_alpha):
         lib = L.load()
         dev = color.device
-        color, depth, alpha = color.contiguous(), depth.contiguous(), alpha.contiguous()
-        H, W = int(color.shape[-2]), int(color.shape[-1])
+        color = M.f32_contiguous("color", color, (3, None, None))
+        H, W = int(color.shape[1]), int(color.shape[2])
+        depth, alpha = M.f32_contiguous("depth", depth, (1, H, W), dev), M.f32_contiguous("alpha", alpha, (1, H, W), dev)
+        target_chw = M.f32_contiguous("target", target_chw, (3, H, W), dev)
         loss = torch.zeros((), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             st = M.stream()
@@ -46,7 +48,8 @@ class _ViewLoss(torch.autograd.Function):
 
 def view_loss_fused(color_chw: torch.Tensor, depth: torch.Tensor, alpha: torch.Tensor, target_chw: torch.Tensor,
                     w_depth: float = 0.1, w_alpha: float = 0.1) -> torch.Tensor:
-    """color (3,H,W) UNclamped rasterizer output, depth/alpha (1,H,W), target (3,H,W) contiguous fp32 on the GPU."""
+    """color (3,H,W) UNclamped rasterizer output, depth/alpha (1,H,W), target (3,H,W): fp32 on the GPU, any strides (a view is
+    copied into contiguous form); another dtype is a TypeError, another shape a ValueError."""
     if not color_chw.is_cuda:
         raise RuntimeError("view_loss_fused runs on ROCm/HIP tensors only")
     return _ViewLoss.apply(color_chw, depth, alpha, target_chw, w_depth, w_alpha)
@@ -57,10 +60,10 @@ class _SurfelViewLoss(torch.autograd.Function):
     def forward(ctx, color, allmap, rays, viewmatrix, target_chw, depth_ratio, w_dist, w_normal, w_depth, w_alpha):
         lib = L.load()
         dev = color.device
-        color, allmap = color.contiguous(), allmap.contiguous()
-        rays = rays.to(device=dev, dtype=torch.float32).contiguous()
-        view = viewmatrix.to(device=dev, dtype=torch.float32).contiguous()
-        H, W = int(color.shape[-2]), int(color.shape[-1])
+        color = M.f32_contiguous("color", color, (3, None, None))
+        H, W = int(color.shape[1]), int(color.shape[2])
+        allmap, target_chw = M.f32_contiguous("allmap", allmap, (7, H, W), dev), M.f32_contiguous("target", target_chw, (3, H, W), dev)
+        rays, view = M.rays_and_view(rays, viewmatrix, H, W, dev)
         w = (float(depth_ratio), float(w_dist), float(w_normal), float(w_depth), float(w_alpha))
         loss = torch.zeros((), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):

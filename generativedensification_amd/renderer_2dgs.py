@@ -66,10 +66,9 @@ class _SurfelMaps(torch.autograd.Function):
     def forward(ctx, allmap, rays, viewmatrix, depth_ratio):
         lib = L.load()
         dev = allmap.device
-        allmap = allmap.contiguous()
-        rays = rays.to(device=dev, dtype=torch.float32).contiguous()
-        view = viewmatrix.to(device=dev, dtype=torch.float32).contiguous()
+        allmap = M.f32_contiguous("allmap", allmap, (7, None, None))
         H, W = int(allmap.shape[1]), int(allmap.shape[2])
+        rays, view = M.rays_and_view(rays, viewmatrix, H, W, dev)
         f32 = dict(dtype=torch.float32, device=dev)
         depth, acc = torch.empty(H, W, 1, **f32), torch.empty(H, W, **f32)
         rn, dn, dist = torch.empty(H, W, 3, **f32), torch.empty(H, W, 3, **f32), torch.empty(H, W, **f32)
