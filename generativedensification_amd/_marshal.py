@@ -6,6 +6,8 @@ import ctypes as C
 
 import torch
 
+from . import _lib as L
+
 raw_stream = torch._C._cuda_getCurrentRawStream   # (torch.cuda.current_stream() builds a Stream object: 9 us per call)
 
 
@@ -38,6 +40,34 @@ def workspace(nbytes: int, dev):
     """A uint8 workspace of `nbytes` on `dev` as (tensor, base, usable bytes); keep the tensor alive through the call."""
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     return (ws, *aligned_base(ws.data_ptr(), nbytes))
+
+
+# torch dtype -> the storage type code of the row kernels (GDR_NORM_F16 / BF16 / F32)
+NORM_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
+               torch.float32: L.GDR_NORM_DTYPES["f32"]}
+
+
+def queried_workspace(query, name, dev, *args):
+    """A workspace of the `query(*args)` bytes a gdr_*_workspace_bytes function `name` asks for, with the slack to align its
+    base; a 0 answer is the library's refusal and raises its text."""
+    nbytes = query(*args)
+    if nbytes == 0:
+        L.check(-1, name)
+    return workspace(nbytes + 256, dev)
+
+
+def dense(t):
+    """`t` (or None) contiguous: itself where it is so already"""
+    return t if t is None or t.is_contiguous() else t.contiguous()
+
+
+def dense_aligned(rows):
+    """`rows` dense from a 16-byte aligned base: itself where it is so already, one copy otherwise"""
+    if rows.numel() and (not rows.is_contiguous() or rows.data_ptr() % 16):
+        rows = rows.contiguous()
+        if rows.data_ptr() % 16:
+            rows = rows.clone()
+    return rows
 
 
 def f32_contiguous(name, t, shape, dev=None):

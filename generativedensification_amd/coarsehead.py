@@ -55,8 +55,8 @@ SH_DIMS = (3, 12, 27, 48)
 # "torch" (the reference's lines, on purpose: the A/B of scripts/bench_coarsehead.py)
 HEAD_BACKEND = "hip"
 
-_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-           torch.float32: L.GDR_NORM_DTYPES["f32"]}
+_DTYPES = M.NORM_DTYPES
+_dense = M.dense
 _NO_CPU = "the HIP coarse head runs on ROCm/HIP tensors only (no CPU fallback)"
 
 
@@ -68,19 +68,11 @@ def in_envelope(rows, C, K, sh_dim):
 
 def _rows(x):
     """x (..., C) as its (rows, C) matrix, dense from a 16-byte aligned base: a view where x is so already, one copy otherwise"""
-    rows = x.reshape(-1, x.shape[-1])
-    if rows.numel() and (not rows.is_contiguous() or rows.data_ptr() % 16):
-        rows = rows.contiguous()
-        if rows.data_ptr() % 16:
-            rows = rows.clone()
-    return rows
+    return M.dense_aligned(x.reshape(-1, x.shape[-1]))
 
 
 def _workspace(lib, what, dt, rows, C, K, sh_dim, dev):
-    nbytes = lib.gdr_coarsehead_workspace_bytes(what, dt, rows, C, K, sh_dim)
-    if nbytes == 0:
-        L.check(-1, "gdr_coarsehead_workspace_bytes")
-    return M.workspace(nbytes + 256, dev)
+    return M.queried_workspace(lib.gdr_coarsehead_workspace_bytes, "gdr_coarsehead_workspace_bytes", dev, what, dt, rows, C, K, sh_dim)
 
 
 def _packed(lib, ws3, backward, dt, C, K, sh_dim, dev):
@@ -89,10 +81,6 @@ def _packed(lib, ws3, backward, dt, C, K, sh_dim, dev):
     args = [a for w in ws3 for a in (w.data_ptr(), _DTYPES[w.dtype])]
     L.check(lib.gdr_coarsehead_pack(*args, C, K, sh_dim, int(backward), base, dt, M.stream()), "gdr_coarsehead_pack")
     return ws, base
-
-
-def _dense(t):
-    return t if t is None or t.is_contiguous() else t.contiguous()
 
 
 def _grad(g, dev):

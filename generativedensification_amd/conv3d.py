@@ -41,8 +41,7 @@ MAX_CHANNELS = L.GDR_CONV3D_MAX_CHANNELS
 MAX_ROWS = (1 << 31) - 1
 BRICK = L.GDR_CONV3D_BRICK          # voxels (D, H, W) of one workgroup of the product kernel
 
-_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-           torch.float32: L.GDR_NORM_DTYPES["f32"]}
+_DTYPES = M.NORM_DTYPES
 _NO_CPU = "the HIP convolution runs on ROCm/HIP tensors only (no CPU fallback)"
 
 
@@ -55,19 +54,11 @@ def in_envelope(B, Cin, Cout, D, H, W):
 def _rows(x):
     """x (B, C, D, H, W) as its (B, D, H, W, C) rows, dense from a 16-byte aligned base: a view of a channels_last_3d x (the
     strides of size-1 axes do not count), one copy of anything else"""
-    rows = x.permute(0, 2, 3, 4, 1)
-    if rows.numel() and (not rows.is_contiguous() or rows.data_ptr() % 16):
-        rows = rows.contiguous()
-        if rows.data_ptr() % 16:
-            rows = rows.clone()
-    return rows
+    return M.dense_aligned(x.permute(0, 2, 3, 4, 1))
 
 
 def _workspace(lib, what, dt, voxels, cin, cout, dev):
-    nbytes = lib.gdr_conv3d_workspace_bytes(what, dt, voxels, cin, cout)
-    if nbytes == 0:
-        L.check(-1, "gdr_conv3d_workspace_bytes")
-    return M.workspace(nbytes + 256, dev)
+    return M.queried_workspace(lib.gdr_conv3d_workspace_bytes, "gdr_conv3d_workspace_bytes", dev, what, dt, voxels, cin, cout)
 
 
 def _product(lib, rows, dt, weight, mirrored, bias, addend, out, dev):
@@ -89,8 +80,7 @@ class _Conv3d(torch.autograd.Function):
         rows = _rows(x)
         B, D, H, W, cin = rows.shape
         cout = weight.shape[0]
-        w = weight if weight.is_contiguous() else weight.contiguous()
-        b = bias if bias is None or bias.is_contiguous() else bias.contiguous()
+        w, b = M.dense(weight), M.dense(bias)
         with torch.cuda.device(dev):
             out = torch.empty(B, D, H, W, cout, dtype=x.dtype, device=dev)
             if out.numel():

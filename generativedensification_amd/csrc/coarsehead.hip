@@ -18,7 +18,7 @@
 //   pack: one launch rounds the three weights to the compute dtype into one zero-padded buffer: [out][in] for the products of
 //     the forward direction, [in][out] for those of the backward; both sides padded to whole sum chunks, so no product
 //     guards an index.
-//   forward: a workgroup owns CH_ROWS = 64 consecutive rows, wave w the 16 rows of tile w.  The rows are staged in LDS, every
+//   forward: a workgroup owns HEAD_ROWS = 64 consecutive rows, wave w the 16 rows of tile w.  The rows are staged in LDS, every
 //     layer reads its operand rows from LDS and leaves its rounded, gated result in LDS for the next; the weight fragments are
 //     read from the packed buffer (global memory: every workgroup reads the same < 30 KB at C = 80).  The last layer's
 //     epilogue leaves the (64, K P) values and the centres in an fp32 LDS stage, and the workgroup copies each of the five
@@ -26,31 +26,24 @@
 //   backward: a workgroup owns a slab of rows and walks it `step` rows at a time (64, 32 or 16: what fits LDS).  Per step it
 //     recomputes h1 and h2, gathers dz3 from the upstream gradients, and runs dz3 -> dz2 -> dz1 -> grad_x, the (row tile,
 //     channel tile) pairs of every product dealt round to the 4 waves.  Every activation is also left transposed ([channel][row])
-//     so that the row is the MFMA's sum index of the weight gradients: a wave keeps CH_TPW 16 x 16 tiles of the three
-//     grad_W in registers over the whole slab (blockIdx.y selects which, when there are more than 4 CH_TPW), thread c the
+//     so that the row is the MFMA's sum index of the weight gradients: a wave keeps HEAD_TPW 16 x 16 tiles of the three
+//     grad_W in registers over the whole slab (blockIdx.y selects which, when there are more than 4 HEAD_TPW), thread c the
 //     column sums of channel c; one partial set per slab; a second launch adds them, 16 segments of the slabs per element in
 //     slab order, then the 16 segment sums.  No atomics.
+// What this file has in common with finehead.hip (the geometry, the tile product, the x-row staging, grad_x, the weight-gradient
+// tile bookkeeping, the fold, the backward's LDS carve) is head_rows.h.
 // Tile sizes, the step and where the weights sit are unmeasured choices.
 #include "gdr_common.h"
 #include "half_bits.h"
 #include "host_util.h"
 #include "mfma_rows.h"
+#include "head_rows.h"
 
 namespace gdr {
 namespace {
 
-constexpr int CH_BLOCK = GDR_BLOCK;
-constexpr int CH_ROWS = GDR_COARSEHEAD_TILE_ROWS;
-constexpr int CH_TPW = 16;                         // weight-gradient tiles a wave accumulates
 constexpr int CH_MAX_SLABS = 1024;
-constexpr int CH_FOLD = 16;                        // fold: elements per block, and segments of the slabs per element
 constexpr int CH_SLAB_MIN = GDR_COARSEHEAD_SLAB_MIN;
-constexpr size_t CH_LDS_MAX = 160 * 1024;
-constexpr size_t CH_LDS_PREFER = 80 * 1024;        // two workgroups per CU
-static_assert(CH_FOLD * CH_FOLD == CH_BLOCK, "the fold's threads are (segment, element)");
-static_assert(CH_ROWS == 64 && CH_BLOCK == 256, "4 waves, 4 row tiles of 16");
-
-template <int DT> using Sc = typename std::conditional<DT == GDR_NORM_F32, double, float>::type;      // the accumulator's element
 
 // the shape and its padded sizes
 struct Geo {
@@ -58,8 +51,6 @@ struct Geo {
     int32_t Cpad, Opad;      // C and K P rounded up to whole sum chunks (32 elements of 16 bits, 16 of f32)
     int32_t C16, O16;        // ... to whole 16 x 16 tiles
 };
-
-__host__ __device__ inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
 Geo geo_of(int dtype, int C, int K, int sh) {
     Geo g;
@@ -78,32 +69,10 @@ __host__ __device__ inline int64_t packed_elems(const Geo& g, bool backward) { r
 // elements of one partial set: grad_W1, grad_W2 (C, C), grad_W3 (K P, C), grad_b1, grad_b2 (C), grad_b3 (K P)
 __host__ __device__ inline int64_t partial_elems(const Geo& g) { return 2 * (int64_t)g.C * g.C + (int64_t)g.KP * g.C + 2 * g.C + g.KP; }
 
-// D += A B over kpad sum elements: A points at the tile's first A row (row stride lda), B at its first B row (the D column),
-// both 16-byte aligned with strides of whole vectors.  Lane (l16, quad) ends with D rows 4 quad .. + 3 of D column l16.
-template <int DT>
-__device__ __forceinline__ void tile_mma(const typename El<DT>::type* A, int lda, const typename El<DT>::type* B, int ldb, int kpad, int l16,
-                                         int quad, typename El<DT>::acc& acc) {
-    constexpr int VE = El<DT>::VE, KC = El<DT>::KC;
-    const typename El<DT>::type* a = A + (int64_t)a_row<DT>(l16) * lda + quad * VE;
-    const typename El<DT>::type* b = B + (int64_t)l16 * ldb + quad * VE;
-    for (int k = 0; k < kpad; k += KC) mma_row<DT>(*reinterpret_cast<const uint4*>(a + k), *reinterpret_cast<const uint4*>(b + k), acc);
-}
-
-// a bias as the forward adds it: rounded to the compute dtype; 0 beyond its n entries
-template <int DT> __device__ __forceinline__ Sc<DT> bias_at(const void* b, int dt, int c, int n) {
-    return c < n ? (Sc<DT>)up<DT>(down<DT>(load_any(b, c, dt))) : (Sc<DT>)0;
-}
-
 // relu of the pre-activation rounded to the compute dtype
 template <int DT> __device__ __forceinline__ typename El<DT>::type relu_rd(Sc<DT> z) {
     const typename El<DT>::type r = down<DT>((float)z);
     return up<DT>(r) > 0.0f ? r : down<DT>(0.0f);
-}
-
-// 4 consecutive elements of an LDS / global row
-template <int DT> __device__ __forceinline__ void store4(typename El<DT>::type* dst, const typename El<DT>::type (&v)[4]) {
-    if constexpr (DT == GDR_NORM_F32) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-    else *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)v[0] | ((uint32_t)v[1] << 16), (uint32_t)v[2] | ((uint32_t)v[3] << 16));
 }
 
 // ---- pack -------------------------------------------------------------------------------------------------------------------------
@@ -117,8 +86,8 @@ struct PackP {
 };
 
 template <int DT>
-__global__ __launch_bounds__(CH_BLOCK) void coarsehead_pack_kernel(const PackP p) {
-    int64_t i = (int64_t)blockIdx.x * CH_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(HEAD_BLOCK) void coarsehead_pack_kernel(const PackP p) {
+    int64_t i = (int64_t)blockIdx.x * HEAD_BLOCK + threadIdx.x;
     if (i >= p.total) return;
     const int64_t at = i, sq = sq_of(p.g);
     const int C = p.g.C, KP = p.g.KP, Cpad = p.g.Cpad, Opad = p.g.Opad;
@@ -167,17 +136,16 @@ struct FwdP {
 __device__ __forceinline__ void copy_out(float* dst, const float* stage, int sw, int64_t e0, int count, int K, int w, int stride, int off, int tid) {
     if (!dst) return;
     dst += e0 * w;
-    for (int i = tid; i < count * w; i += CH_BLOCK) {
+    for (int i = tid; i < count * w; i += HEAD_BLOCK) {
         const int el = i / w, c = i - el * w, r = el / K, k = el - r * K;
         dst[i] = stage[r * sw + k * stride + off + c];
     }
 }
 
 template <int DT>
-__global__ __launch_bounds__(CH_BLOCK) void coarsehead_forward_kernel(const FwdP p) {
+__global__ __launch_bounds__(HEAD_BLOCK) void coarsehead_forward_kernel(const FwdP p) {
     using E = typename El<DT>::type;
     using T = Sc<DT>;
-    constexpr int VE = El<DT>::VE;
     extern __shared__ __attribute__((aligned(16))) unsigned char ch_lds[];
     E* bufA = (E*)ch_lds;                              // h1; later the fp32 stage
     E* bufB = (E*)(ch_lds + p.region0);                // x, then h2
@@ -185,19 +153,13 @@ __global__ __launch_bounds__(CH_BLOCK) void coarsehead_forward_kernel(const FwdP
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, quad = lane >> 4;
     const Geo& g = p.g;
     const int lda = p.lda, Cpad = g.Cpad;
-    const int64_t row0 = (int64_t)blockIdx.x * CH_ROWS;
+    const int64_t row0 = (int64_t)blockIdx.x * HEAD_ROWS;
     const E* X = (const E*)p.x;
     const E* W1 = (const E*)p.packed;
     const E* W2 = W1 + sq_of(g);
     const E* W3 = W2 + sq_of(g);
 
-    const int vpr = Cpad / VE;
-    for (int v = tid; v < CH_ROWS * vpr; v += CH_BLOCK) {
-        const int r = v / vpr, c = (v - r * vpr) * VE;
-        uint4 val = make_uint4(0, 0, 0, 0);
-        if (row0 + r < p.n && c < g.C) val = *reinterpret_cast<const uint4*>(X + (row0 + r) * g.C + c);
-        *reinterpret_cast<uint4*>(bufB + r * lda + c) = val;
-    }
+    stage_rows<DT>(X, row0, p.n, HEAD_ROWS, g.C, Cpad, bufB, lda, false, nullptr, 0, tid);
     __syncthreads();
     const int r = 16 * wave + l16;                     // this lane's row of the tile
 #pragma unroll 1
@@ -242,7 +204,7 @@ __global__ __launch_bounds__(CH_BLOCK) void coarsehead_forward_kernel(const FwdP
     }
     __syncthreads();
     const int64_t left = p.n - row0;
-    const int count = (int)(left < CH_ROWS ? left : CH_ROWS) * g.K;
+    const int count = (int)(left < HEAD_ROWS ? left : HEAD_ROWS) * g.K;
     const int64_t e0 = row0 * g.K;
     copy_out(p.out[0], stage, p.sw, e0, count, g.K, 3, g.P, 0, tid);
     copy_out(p.out[1], stage, p.sw, e0, count, g.K, g.sh, g.P, 3, tid);
@@ -251,7 +213,7 @@ __global__ __launch_bounds__(CH_BLOCK) void coarsehead_forward_kernel(const FwdP
     copy_out(p.out[3], stage, p.sw, e0, count, g.K, 4, g.P, 7 + g.sh, tid);
     copy_out(p.centers, stage + g.KP, p.sw, e0, count, g.K, 3, 3, 0, tid);
     if (p.mask)
-        for (int i = tid; i < count; i += CH_BLOCK) {
+        for (int i = tid; i < count; i += HEAD_BLOCK) {
             const int rr = i / g.K, k = i - rr * g.K;
             const float op = stage[rr * p.sw + k * g.P + 3 + g.sh];
             p.mask[e0 + i] = 1.0f / (1.0f + expf(-op)) > (float)p.threshold ? 1 : 0;
@@ -284,7 +246,7 @@ __device__ __forceinline__ void gather_dz3(const BwdP& p, const float* gsrc, boo
     const int64_t left = r_end - r0;
     const int count = (int)(left < p.step ? left : p.step) * K;
     const int64_t base = r0 * K * w;
-    for (int i = tid; i < p.step * K * w; i += CH_BLOCK) {
+    for (int i = tid; i < p.step * K * w; i += HEAD_BLOCK) {
         const int el = i / w, c = i - el * w, r = el / K, k = el - r * K;
         T gv = 0;
         if (el < count) {
@@ -303,11 +265,10 @@ __device__ __forceinline__ void gather_dz3(const BwdP& p, const float* gsrc, boo
 }
 
 template <int DT>
-__global__ __launch_bounds__(CH_BLOCK) void coarsehead_backward_kernel(const BwdP p) {
+__global__ __launch_bounds__(HEAD_BLOCK) void coarsehead_backward_kernel(const BwdP p) {
     using E = typename El<DT>::type;
     using T = Sc<DT>;
     using Acc = typename El<DT>::acc;
-    constexpr int VE = El<DT>::VE;
     extern __shared__ __attribute__((aligned(16))) unsigned char ch_lds[];
     const Geo& g = p.g;
     const int C = g.C, Cpad = g.Cpad, Opad = g.Opad, KP = g.KP, step = p.step, lda = p.lda, ldz = p.ldz, ldt = p.ldt, rt = step / 16;
@@ -332,32 +293,27 @@ __global__ __launch_bounds__(CH_BLOCK) void coarsehead_backward_kernel(const Bwd
     const int64_t r_end = r_begin + p.slab_rows < p.n ? r_begin + p.slab_rows : p.n;
 
     // the weight-gradient tiles of this wave: tile t of [grad_W1 | grad_W2 | grad_W3], 16 x 16 each, (out tile, in tile) row-major
-    const int c16 = g.C16 / 16, n1 = c16 * c16, ntiles = 2 * n1 + (g.O16 / 16) * c16;
-    const int t_first = (blockIdx.y * 4 + wave) * CH_TPW;
-    Acc accW[CH_TPW];
+    const int c16 = g.C16 / 16, n1 = c16 * c16;
+    WgTiles<DT> wg = {};
+    wg.n = 3; wg.ntiles = 2 * n1 + (g.O16 / 16) * c16; wg.C = C; wg.c16 = c16;
+    wg.s[0] = {z1T, xT, 0, C, 0};
+    wg.s[1] = {z2T, h1T, n1, C, (int64_t)C * C};
+    wg.s[2] = {z3T, h2T, 2 * n1, KP, 2 * (int64_t)C * C};
+    const int t_first = (blockIdx.y * 4 + wave) * HEAD_TPW;
+    Acc accW[HEAD_TPW];
 #pragma unroll
-    for (int i = 0; i < CH_TPW; ++i) accW[i] = Acc{0, 0, 0, 0};
+    for (int i = 0; i < HEAD_TPW; ++i) accW[i] = Acc{0, 0, 0, 0};
     T db1 = 0, db2 = 0, db3 = 0;
 
     // the pad columns of dz3 are never written again
-    for (int i = tid; i < step * (Opad - KP); i += CH_BLOCK) {
+    for (int i = tid; i < step * (Opad - KP); i += HEAD_BLOCK) {
         const int r = i / (Opad - KP), j = KP + i - r * (Opad - KP);
         RZ[r * ldz + j] = down<DT>(0.0f);
         z3T[j * ldt + r] = down<DT>(0.0f);
     }
 
     for (int64_t r0 = r_begin; r0 < r_end; r0 += step) {
-        const int vpr = Cpad / VE;
-        for (int v = tid; v < step * vpr; v += CH_BLOCK) {
-            const int r = v / vpr, c = (v - r * vpr) * VE;
-            union { uint4 v; E e[VE]; } u;
-            u.v = make_uint4(0, 0, 0, 0);
-            if (r0 + r < r_end && c < C) u.v = *reinterpret_cast<const uint4*>(X + (r0 + r) * C + c);
-            *reinterpret_cast<uint4*>(R0 + r * lda + c) = u.v;
-            if (sums)
-#pragma unroll
-                for (int e = 0; e < VE; ++e) xT[(c + e) * ldt + r] = u.e[e];
-        }
+        stage_rows<DT>(X, r0, r_end, step, C, Cpad, R0, lda, sums, xT, ldt, tid);
         __syncthreads();
         // h1 -> R1 and h1T
         for (int pr = wave; pr < (Cpad / 16) * rt; pr += 4) {
@@ -416,31 +372,9 @@ __global__ __launch_bounds__(CH_BLOCK) void coarsehead_backward_kernel(const Bwd
         }
         __syncthreads();
         // grad_x = dz1 W1
-        if (p.grad_x && blockIdx.y == 0)
-            for (int pr = wave; pr < (g.C16 / 16) * rt; pr += 4) {
-                const int ti = pr % rt, jt = pr / rt, ch = 16 * jt + 4 * quad;
-                const int64_t row = r0 + 16 * ti + l16;
-                Acc acc = {0, 0, 0, 0};
-                tile_mma<DT>(W1t + (int64_t)16 * jt * Cpad, Cpad, R1 + 16 * ti * lda, lda, Cpad, l16, quad, acc);
-                if (row < r_end && ch < C) {          // C is a multiple of 8: the 4 channels are in or out together
-                    E d[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) d[e] = down<DT>((float)acc[e]);
-                    store4<DT>((E*)p.grad_x + row * C + ch, d);
-                }
-            }
+        if (p.grad_x && blockIdx.y == 0) grad_x_tiles<DT>(W1t, R1, lda, p.grad_x, r0, r_end, rt, C, g.C16, Cpad, wave, l16, quad);
         if (sums) {
-#pragma unroll
-            for (int i = 0; i < CH_TPW; ++i) {
-                int t = t_first + i;
-                if (t >= ntiles) continue;            // (uniform over the wave)
-                const E* A;
-                const E* B;
-                if (t < n1) { A = z1T; B = xT; }
-                else if (t < 2 * n1) { A = z2T; B = h1T; t -= n1; }
-                else { A = z3T; B = h2T; t -= 2 * n1; }
-                tile_mma<DT>(A + 16 * (t / c16) * ldt, ldt, B + 16 * (t % c16) * ldt, ldt, step, l16, quad, accW[i]);
-            }
+            wgrad_step<DT>(wg, t_first, ldt, step, l16, quad, accW);
             if (blockIdx.y == 0) {
                 if (tid < C)
                     for (int r = 0; r < step; ++r) {
@@ -455,21 +389,7 @@ __global__ __launch_bounds__(CH_BLOCK) void coarsehead_backward_kernel(const Bwd
     }
     if (!sums) return;
     T* part = (T*)p.part + (int64_t)blockIdx.x * partial_elems(g);
-#pragma unroll
-    for (int i = 0; i < CH_TPW; ++i) {
-        int t = t_first + i;
-        if (t >= ntiles) continue;
-        int64_t base = 0;
-        int olim = C;
-        if (t >= 2 * n1) { base = 2 * (int64_t)C * C; olim = KP; t -= 2 * n1; }
-        else if (t >= n1) { base = (int64_t)C * C; t -= n1; }
-        const int in = 16 * (t % c16) + l16;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int o = 16 * (t / c16) + 4 * quad + e;
-            if (o < olim && in < C) part[base + (int64_t)o * C + in] = accW[i][e];
-        }
-    }
+    wgrad_store<DT>(wg, t_first, part, l16, quad, accW);
     if (blockIdx.y == 0) {
         T* pb = part + 2 * (int64_t)C * C + (int64_t)KP * C;
         if (tid < C) {
@@ -480,45 +400,7 @@ __global__ __launch_bounds__(CH_BLOCK) void coarsehead_backward_kernel(const Bwd
     }
 }
 
-// the six parameter gradients = the slabs' partial sets added in slab order, each rounded once to its dtype
-struct FoldP {
-    const void* part;
-    void* out[6];              // grad_W1, grad_W2, grad_W3, grad_b1, grad_b2, grad_b3; any may be NULL
-    int32_t out_dtype[6];
-    int64_t size[6];
-    int64_t total;
-    int32_t slabs;
-};
-
-// a block owns CH_FOLD elements; 16 threads per element add one segment of the slabs each, in slab order, then the first adds
-// the 16 segment sums in segment order
-template <typename T>
-__global__ __launch_bounds__(CH_BLOCK) void coarsehead_fold_kernel(const FoldP p) {
-    __shared__ T sSeg[CH_FOLD][CH_FOLD];
-    const int el = threadIdx.x % CH_FOLD, seg = threadIdx.x / CH_FOLD;
-    int64_t i = (int64_t)blockIdx.x * CH_FOLD + el;
-    const int per = (p.slabs + CH_FOLD - 1) / CH_FOLD, b0 = seg * per, b1 = b0 + per < p.slabs ? b0 + per : p.slabs;
-    T s = 0;
-    if (i < p.total)
-        for (int b = b0; b < b1; ++b) s += ((const T*)p.part)[(int64_t)b * p.total + i];
-    sSeg[seg][el] = s;
-    __syncthreads();
-    if (seg != 0 || i >= p.total) return;
-    T sum = 0;
-    for (int k = 0; k < CH_FOLD; ++k) sum += sSeg[k][el];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        if (i < p.size[k]) {
-            if (p.out[k]) store_any(p.out[k], i, p.out_dtype[k], (float)sum);
-            return;
-        }
-        i -= p.size[k];
-    }
-}
-
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-size_t esize(int dtype) { return dtype == GDR_NORM_F32 ? 4 : 2; }
-
 bool bad_shape(int32_t C, int32_t K, int32_t sh) {
     if (C < 8 || C > GDR_COARSEHEAD_MAX_C || C % 8 || K < 1 || K > 4) return true;
     if (sh != 3 && sh != 12 && sh != 27 && sh != 48) return true;
@@ -530,58 +412,21 @@ bool bad_rows_count(int64_t rows, int32_t K) { return rows > ((INT64_C(1) << 31)
 const char* const CH_ENVELOPE = "coarsehead: C must be a multiple of 8 in 8..GDR_COARSEHEAD_MAX_C, K in 1..4, sh_dim one of 3, 12, 27, 48, "
                                 "K P <= GDR_COARSEHEAD_MAX_OUT and rows K below 2^31";
 
-int slabs_of(int64_t n) {
-    const int64_t s = (n + CH_SLAB_MIN - 1) / CH_SLAB_MIN;
-    return s < 1 ? 1 : (s > CH_MAX_SLABS ? CH_MAX_SLABS : (int)s);
-}
+int slabs_of(int64_t n) { return slabs_of(n, CH_SLAB_MIN, CH_MAX_SLABS); }
 
 struct FwdLds { int lda, sw; size_t region0, total; };
 FwdLds fwd_lds(int dtype, const Geo& g) {
     FwdLds l;
     l.lda = g.Cpad + (dtype == GDR_NORM_F32 ? 4 : 8);
     l.sw = g.KP + 3 * g.K + 1;
-    const size_t rows = (size_t)CH_ROWS * l.lda * esize(dtype), stage = (size_t)CH_ROWS * l.sw * sizeof(float);
+    const size_t rows = (size_t)HEAD_ROWS * l.lda * esize(dtype), stage = (size_t)HEAD_ROWS * l.sw * sizeof(float);
     l.region0 = align_up(rows > stage ? rows : stage, 16);
     l.total = l.region0 + rows;
     return l;
 }
 
-struct BwdLds { int step, lda, ldz, ldt; size_t total; };
-size_t bwd_bytes(int dtype, const Geo& g, int step, BwdLds* l) {
-    const int ve = dtype == GDR_NORM_F32 ? 4 : 8;
-    l->step = step; l->lda = g.Cpad + ve; l->ldz = g.Opad + ve; l->ldt = step + ve;
-    l->total = esize(dtype) * ((size_t)2 * step * l->lda + (size_t)step * l->ldz + (size_t)(5 * g.Cpad + g.Opad) * l->ldt);
-    return l->total;
-}
-// the rows per step: the most that leave room for two workgroups per CU, or else the fewest
-BwdLds bwd_lds(int dtype, const Geo& g) {
-    BwdLds l;
-    const int least = dtype == GDR_NORM_F32 ? 16 : 32;
-    for (int step = 64; step > least; step /= 2)
-        if (bwd_bytes(dtype, g, step, &l) <= CH_LDS_PREFER) return l;
-    bwd_bytes(dtype, g, least, &l);
-    return l;
-}
-
-template <typename K> hipError_t allow_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-#define GDR_COARSEHEAD_DT(KERNEL, GRID, LDS, ST, P)                                                                        \
-    do {                                                                                                                   \
-        hipError_t e_;                                                                                                     \
-        if (dtype == GDR_NORM_F16) {                                                                                       \
-            if ((e_ = allow_lds(KERNEL<GDR_NORM_F16>, LDS)) != hipSuccess) { set_error(#KERNEL, e_); return GDR_ERR_HIP; } \
-            hipLaunchKernelGGL(KERNEL<GDR_NORM_F16>, GRID, dim3(CH_BLOCK), LDS, ST, P);                                    \
-        } else if (dtype == GDR_NORM_BF16) {                                                                               \
-            if ((e_ = allow_lds(KERNEL<GDR_NORM_BF16>, LDS)) != hipSuccess) { set_error(#KERNEL, e_); return GDR_ERR_HIP; } \
-            hipLaunchKernelGGL(KERNEL<GDR_NORM_BF16>, GRID, dim3(CH_BLOCK), LDS, ST, P);                                   \
-        } else {                                                                                                           \
-            if ((e_ = allow_lds(KERNEL<GDR_NORM_F32>, LDS)) != hipSuccess) { set_error(#KERNEL, e_); return GDR_ERR_HIP; } \
-            hipLaunchKernelGGL(KERNEL<GDR_NORM_F32>, GRID, dim3(CH_BLOCK), LDS, ST, P);                                    \
-        }                                                                                                                  \
-    } while (0)
+// the backward's steps: xT, h1T, h2T, z1T and z2T are its transposed Cpad-channel buffers
+BwdLds bwd_lds(int dtype, const Geo& g) { return bwd_lds(dtype, g.Cpad, g.Opad, 5); }
 
 }  // namespace
 }  // namespace gdr
@@ -615,10 +460,10 @@ int gdr_coarsehead_pack(const void* w1, int32_t w1_dtype, const void* w2, int32_
     PackP p = {};
     p.w[0] = w1; p.w[1] = w2; p.w[2] = w3; p.w_dtype[0] = w1_dtype; p.w_dtype[1] = w2_dtype; p.w_dtype[2] = w3_dtype;
     p.packed = packed; p.g = geo_of(dtype, C, K, sh_dim); p.backward = backward ? 1 : 0; p.total = packed_elems(p.g, backward != 0);
-    const dim3 grid((uint32_t)div_up(p.total, (int64_t)CH_BLOCK));
-    if (dtype == GDR_NORM_F16) hipLaunchKernelGGL(coarsehead_pack_kernel<GDR_NORM_F16>, grid, dim3(CH_BLOCK), 0, (hipStream_t)stream, p);
-    else if (dtype == GDR_NORM_BF16) hipLaunchKernelGGL(coarsehead_pack_kernel<GDR_NORM_BF16>, grid, dim3(CH_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(coarsehead_pack_kernel<GDR_NORM_F32>, grid, dim3(CH_BLOCK), 0, (hipStream_t)stream, p);
+    const dim3 grid((uint32_t)div_up(p.total, (int64_t)HEAD_BLOCK));
+    if (dtype == GDR_NORM_F16) hipLaunchKernelGGL(coarsehead_pack_kernel<GDR_NORM_F16>, grid, dim3(HEAD_BLOCK), 0, (hipStream_t)stream, p);
+    else if (dtype == GDR_NORM_BF16) hipLaunchKernelGGL(coarsehead_pack_kernel<GDR_NORM_BF16>, grid, dim3(HEAD_BLOCK), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(coarsehead_pack_kernel<GDR_NORM_F32>, grid, dim3(HEAD_BLOCK), 0, (hipStream_t)stream, p);
     return launch_status("coarsehead_pack_kernel");
 }
 
@@ -643,9 +488,9 @@ int gdr_coarsehead_forward(const void* x, int32_t dtype, const void* packed, con
     p.opacity_shift = opacity_shift; p.scaling_shift = scaling_shift; p.half_cell = half_cell; p.threshold = threshold;
     p.g = geo_of(dtype, C, K, sh_dim);
     const FwdLds l = fwd_lds(dtype, p.g);
-    if (l.total > CH_LDS_MAX) return unsupported("coarsehead_forward: the tile does not fit LDS");
+    if (l.total > HEAD_LDS_MAX) return unsupported("coarsehead_forward: the tile does not fit LDS");
     p.lda = l.lda; p.sw = l.sw; p.region0 = (int64_t)l.region0;
-    GDR_COARSEHEAD_DT(coarsehead_forward_kernel, dim3((uint32_t)div_up(rows, (int64_t)CH_ROWS)), l.total, (hipStream_t)stream, p);
+    GDR_HEAD_DT(coarsehead_forward_kernel, dim3((uint32_t)div_up(rows, (int64_t)HEAD_ROWS)), l.total, (hipStream_t)stream, p);
     return launch_status("coarsehead_forward_kernel");
 }
 
@@ -670,13 +515,13 @@ int gdr_coarsehead_backward(const void* x, int32_t dtype, const void* packed, co
     p.gout[3] = (const float*)grad_rotation; p.gout[4] = (const float*)grad_opacity; p.gcenters = (const float*)grad_centers;
     p.grad_x = grad_x; p.part = workspace; p.n = rows; p.half_cell = half_cell; p.g = geo_of(dtype, C, K, sh_dim);
     const BwdLds l = bwd_lds(dtype, p.g);
-    if (l.total > CH_LDS_MAX) return unsupported("coarsehead_backward: the step does not fit LDS");
+    if (l.total > HEAD_LDS_MAX) return unsupported("coarsehead_backward: the step does not fit LDS");
     p.step = l.step; p.lda = l.lda; p.ldz = l.ldz; p.ldt = l.ldt;
     const int slabs = slabs_of(rows);
-    p.slab_rows = (int64_t)align_up((size_t)((rows + slabs - 1) / slabs), CH_ROWS);
+    p.slab_rows = (int64_t)align_up((size_t)((rows + slabs - 1) / slabs), HEAD_ROWS);
     const int c16 = p.g.C16 / 16, ntiles = 2 * c16 * c16 + (p.g.O16 / 16) * c16;
-    const int groups = workspace ? div_up(ntiles, 4 * CH_TPW) : 1;
-    GDR_COARSEHEAD_DT(coarsehead_backward_kernel, dim3(slabs, groups), l.total, (hipStream_t)stream, p);
+    const int groups = workspace ? div_up(ntiles, 4 * HEAD_TPW) : 1;
+    GDR_HEAD_DT(coarsehead_backward_kernel, dim3(slabs, groups), l.total, (hipStream_t)stream, p);
     return launch_status("coarsehead_backward_kernel");
 }
 
@@ -684,29 +529,19 @@ int gdr_coarsehead_fold(const void* workspace, size_t workspace_bytes, int32_t d
                         void* grad_w1, int32_t grad_w1_dtype, void* grad_b1, int32_t grad_b1_dtype, void* grad_w2, int32_t grad_w2_dtype,
                         void* grad_b2, int32_t grad_b2_dtype, void* grad_w3, int32_t grad_w3_dtype, void* grad_b3, int32_t grad_b3_dtype,
                         void* stream) {
-    void* out[6] = {grad_w1, grad_w2, grad_w3, grad_b1, grad_b2, grad_b3};
+    FoldP p = {};                  // in the order of a partial set
+    p.count = 6;
+    void* const out[6] = {grad_w1, grad_w2, grad_w3, grad_b1, grad_b2, grad_b3};
     const int32_t dts[6] = {grad_w1_dtype, grad_w2_dtype, grad_w3_dtype, grad_b1_dtype, grad_b2_dtype, grad_b3_dtype};
-    if (bad_dtype(dtype)) return invalid_arg("coarsehead_fold: unknown dtype");
-    for (int k = 0; k < 6; ++k)
-        if (out[k] && bad_dtype(dts[k])) return invalid_arg("coarsehead_fold: unknown dtype");
+    for (int k = 0; k < 6; ++k) { p.out[k] = out[k]; p.out_dtype[k] = dts[k]; }
+    if (fold_bad_dtype(dtype, p)) return invalid_arg("coarsehead_fold: unknown dtype");
     if (rows < 0) return invalid_arg("coarsehead_fold: rows must be >= 0");
     if (bad_shape(C, K, sh_dim) || bad_rows_count(rows, K)) return unsupported(CH_ENVELOPE);
-    if (!workspace) return invalid_arg("coarsehead_fold: NULL workspace");
-    if (misaligned(workspace, 255)) return unsupported("coarsehead_fold: the workspace must start on 256 bytes");
-    for (int k = 0; k < 6; ++k)
-        if (out[k] && misaligned(out[k], esize(dts[k]) - 1)) return unsupported("coarsehead_fold: a gradient must be aligned to its element");
-    if (workspace_bytes < gdr_coarsehead_workspace_bytes(GDR_COARSEHEAD_WS_PARTIALS, dtype, rows, C, K, sh_dim))
-        return workspace_too_small("coarsehead_fold: workspace smaller than gdr_coarsehead_workspace_bytes");
     const Geo g = geo_of(dtype, C, K, sh_dim);
-    FoldP p = {};
-    p.part = workspace;
-    for (int k = 0; k < 6; ++k) { p.out[k] = out[k]; p.out_dtype[k] = dts[k]; }
     p.size[0] = p.size[1] = (int64_t)C * C; p.size[2] = (int64_t)g.KP * C; p.size[3] = p.size[4] = C; p.size[5] = g.KP;
-    p.total = partial_elems(g); p.slabs = slabs_of(rows);
-    const dim3 grid((uint32_t)div_up(p.total, (int64_t)CH_FOLD));
-    if (dtype == GDR_NORM_F32) hipLaunchKernelGGL(coarsehead_fold_kernel<double>, grid, dim3(CH_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(coarsehead_fold_kernel<float>, grid, dim3(CH_BLOCK), 0, (hipStream_t)stream, p);
-    return launch_status("coarsehead_fold_kernel");
+    p.slabs = slabs_of(rows);
+    return head_fold("coarsehead", workspace, workspace_bytes, gdr_coarsehead_workspace_bytes(GDR_COARSEHEAD_WS_PARTIALS, dtype, rows, C, K, sh_dim),
+                     dtype, p, stream);
 }
 
 }  // extern "C"

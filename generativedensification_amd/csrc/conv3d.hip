@@ -300,8 +300,6 @@ __global__ __launch_bounds__(CV_BLOCK) void conv3d_bias_sum_kernel(const double*
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-size_t esize(int dtype) { return dtype == GDR_NORM_F32 ? 4 : 2; }
-
 bool bad_channels(int32_t C) { return C < 8 || C > GDR_CONV3D_MAX_CHANNELS || C % 8; }
 
 // voxels of a (B, D, H, W) volume, or -1 beyond the envelope

@@ -640,8 +640,6 @@ __global__ __launch_bounds__(DC_BLOCK) void deconv3d_colsum_fold_kernel(const Fo
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-size_t esize(int dtype) { return dtype == GDR_NORM_F32 ? 4 : 2; }
-
 bool bad_cin(int32_t C) { return C < 8 || C > GDR_DECONV3D_MAX_CIN || C % 8; }
 bool bad_cout(int32_t C) { return C < 8 || C > GDR_DECONV3D_MAX_COUT || C % 8; }
 

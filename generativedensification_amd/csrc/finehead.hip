@@ -12,12 +12,12 @@
 //    Structure (256 threads = 4 waves; D rows are channels, D columns data rows, as in coarsehead.hip):
 //      pack: one launch rounds both weights to the compute dtype into one zero-padded buffer, [out][in] for the products of the
 //        forward direction and [in][out] for those of the backward, padded to whole sum chunks so no product guards an index.
-//      forward: a workgroup owns FH_ROWS = 64 consecutive rows, wave w the 16 rows of tile w.  The rows are staged in LDS, the
+//      forward: a workgroup owns HEAD_ROWS = 64 consecutive rows, wave w the 16 rows of tile w.  The rows are staged in LDS, the
 //        hidden row is left in LDS for the last layer and never leaves the workgroup.
 //      backward: a workgroup owns a slab of rows and walks it `step` rows at a time (64, 32 or 16: what fits LDS).  Per step it
 //        recomputes z1 and h, stages g, and runs dh -> dz1 -> grad_x.  x, h, dz1 and g are also left transposed
-//        ([channel][row]) so that the row is the MFMA's sum index of the weight gradients: a wave keeps FH_TPW 16 x 16 tiles of
-//        [grad_W1 | grad_W2] in registers over the whole slab and blockIdx.y selects which 4 FH_TPW tiles a workgroup owns
+//        ([channel][row]) so that the row is the MFMA's sum index of the weight gradients: a wave keeps HEAD_TPW 16 x 16 tiles of
+//        [grad_W1 | grad_W2] in registers over the whole slab and blockIdx.y selects which 4 HEAD_TPW tiles a workgroup owns
 //        (every tile group recomputes the step: 5 groups at C = 256, P = 20); thread c the column sums of channel c.  One partial
 //        set per slab; a second launch adds them, 16 segments of the slabs per element in slab order, then the 16 segment sums.
 //        No atomics.
@@ -32,30 +32,23 @@
 //        before an address is formed.
 //      backward (1 launch): a thread per element of every gradient wanted; a coarse row reads row rank_rest[rank_masked[i]] of the
 //        upstream gradient or writes zero.
+// What the head has in common with coarsehead.hip (the geometry, the tile product, the x-row staging, grad_x, the weight-gradient
+// tile bookkeeping, the fold, the backward's LDS carve) is head_rows.h.
 // Tile sizes, the step, the slab length and where the weights sit are unmeasured choices.
 #include "gdr_common.h"
 #include "half_bits.h"
 #include "host_util.h"
 #include "mfma_rows.h"
+#include "head_rows.h"
 
 namespace gdr {
 namespace {
 
-constexpr int FH_BLOCK = GDR_BLOCK;
-constexpr int FH_ROWS = GDR_FINEHEAD_TILE_ROWS;
-constexpr int FH_TPW = 16;                         // weight-gradient tiles a wave accumulates
 constexpr int FH_MAX_SLABS = 256;
-constexpr int FH_FOLD = 16;                        // fold: elements per block, and segments of the slabs per element
 constexpr int FH_SLAB_MIN = GDR_FINEHEAD_SLAB_MIN;
 constexpr int FH_CHUNK = GDR_FINEHEAD_SCAN_CHUNK;  // rows per workgroup of the scans
 constexpr int FH_LEVELS = GDR_FINEHEAD_MAX_LEVELS;
-constexpr size_t FH_LDS_MAX = 160 * 1024;
-constexpr size_t FH_LDS_PREFER = 80 * 1024;        // two workgroups per CU
-static_assert(FH_FOLD * FH_FOLD == FH_BLOCK, "the fold's threads are (segment, element)");
-static_assert(FH_ROWS == 64 && FH_BLOCK == 256, "4 waves, 4 row tiles of 16");
-static_assert(FH_CHUNK == 4 * FH_BLOCK, "a scan thread owns 4 rows");
-
-template <int DT> using Sc = typename std::conditional<DT == GDR_NORM_F32, double, float>::type;      // the accumulator's element
+static_assert(FH_CHUNK == 4 * HEAD_BLOCK, "a scan thread owns 4 rows");
 
 // the shape and its padded sizes
 struct Geo {
@@ -63,8 +56,6 @@ struct Geo {
     int32_t Cpad, Opad;      // C and P rounded up to whole sum chunks (32 elements of 16 bits, 16 of f32)
     int32_t C16, O16;        // ... to whole 16 x 16 tiles
 };
-
-__host__ __device__ inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
 Geo geo_of(int dtype, int C, int sh) {
     Geo g;
@@ -83,30 +74,6 @@ __host__ __device__ inline int64_t packed_elems(const Geo& g, bool backward) { r
 // elements of one partial set: grad_W1 (C, C), grad_W2 (P, C), grad_b1 (C), grad_b2 (P)
 __host__ __device__ inline int64_t partial_elems(const Geo& g) { return (int64_t)g.C * g.C + (int64_t)g.P * g.C + g.C + g.P; }
 
-// D += A B over kpad sum elements: A points at the tile's first A row (row stride lda), B at its first B row (the D column),
-// both 16-byte aligned with strides of whole vectors.  Lane (l16, quad) ends with D rows 4 quad .. + 3 of D column l16.
-// kpad is at least one chunk (Cpad, Opad and the step all are), and the loop says so: with a `for`, the compiler guards the loop
-// with a branch round it, the accumulator reads of the epilogue land in the block where the two paths join, and the first two
-// of them are issued without the wait states an MFMA result needs (seen in the forward's last layer: columns 4 q and 4 q + 1
-// came out as the bias alone).  A loop that always runs once leaves the epilogue one predecessor, and the reads get their nops.
-template <int DT>
-__device__ __forceinline__ void tile_mma(const typename El<DT>::type* A, int lda, const typename El<DT>::type* B, int ldb, int kpad, int l16,
-                                         int quad, typename El<DT>::acc& acc) {
-    constexpr int VE = El<DT>::VE, KC = El<DT>::KC;
-    const typename El<DT>::type* a = A + (int64_t)a_row<DT>(l16) * lda + quad * VE;
-    const typename El<DT>::type* b = B + (int64_t)l16 * ldb + quad * VE;
-    int k = 0;
-    do {
-        mma_row<DT>(*reinterpret_cast<const uint4*>(a + k), *reinterpret_cast<const uint4*>(b + k), acc);
-        k += KC;
-    } while (k < kpad);
-}
-
-// a bias as the forward adds it: rounded to the compute dtype; 0 beyond its n entries
-template <int DT> __device__ __forceinline__ Sc<DT> bias_at(const void* b, int dt, int c, int n) {
-    return c < n ? (Sc<DT>)up<DT>(down<DT>(load_any(b, c, dt))) : (Sc<DT>)0;
-}
-
 // torch's default GELU and its derivative, in the accumulator's type
 __device__ __forceinline__ float gelu_of(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752440f)); }
 __device__ __forceinline__ double gelu_of(double z) { return 0.5 * z * (1.0 + erf(z * 0.70710678118654752440)); }
@@ -115,12 +82,6 @@ __device__ __forceinline__ float gelu_slope(float z) {
 }
 __device__ __forceinline__ double gelu_slope(double z) {
     return 0.5 * (1.0 + erf(z * 0.70710678118654752440)) + z * (exp(-0.5 * z * z) * 0.39894228040143267794);
-}
-
-// 4 consecutive elements of an LDS / global row
-template <int DT> __device__ __forceinline__ void store4(typename El<DT>::type* dst, const typename El<DT>::type (&v)[4]) {
-    if constexpr (DT == GDR_NORM_F32) *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-    else *reinterpret_cast<uint2*>(dst) = make_uint2((uint32_t)v[0] | ((uint32_t)v[1] << 16), (uint32_t)v[2] | ((uint32_t)v[3] << 16));
 }
 
 // ---- pack -------------------------------------------------------------------------------------------------------------------------
@@ -134,8 +95,8 @@ struct PackP {
 };
 
 template <int DT>
-__global__ __launch_bounds__(FH_BLOCK) void finehead_pack_kernel(const PackP p) {
-    int64_t i = (int64_t)blockIdx.x * FH_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(HEAD_BLOCK) void finehead_pack_kernel(const PackP p) {
+    int64_t i = (int64_t)blockIdx.x * HEAD_BLOCK + threadIdx.x;
     if (i >= p.total) return;
     const int64_t at = i, sq = sq_of(p.g);
     const int C = p.g.C, P = p.g.P, Cpad = p.g.Cpad, Opad = p.g.Opad;
@@ -173,28 +134,21 @@ struct FwdP {
 };
 
 template <int DT>
-__global__ __launch_bounds__(FH_BLOCK) void finehead_forward_kernel(const FwdP p) {
+__global__ __launch_bounds__(HEAD_BLOCK) void finehead_forward_kernel(const FwdP p) {
     using E = typename El<DT>::type;
     using T = Sc<DT>;
-    constexpr int VE = El<DT>::VE;
     extern __shared__ __attribute__((aligned(16))) unsigned char fh_lds[];
     E* bufX = (E*)fh_lds;                              // x
-    E* bufH = bufX + FH_ROWS * p.lda;                  // h
+    E* bufH = bufX + HEAD_ROWS * p.lda;                  // h
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, quad = lane >> 4;
     const Geo& g = p.g;
     const int lda = p.lda, Cpad = g.Cpad;
-    const int64_t row0 = (int64_t)blockIdx.x * FH_ROWS;
+    const int64_t row0 = (int64_t)blockIdx.x * HEAD_ROWS;
     const E* X = (const E*)p.x;
     const E* W1 = (const E*)p.packed;
     const E* W2 = W1 + sq_of(g);
 
-    const int vpr = Cpad / VE;
-    for (int v = tid; v < FH_ROWS * vpr; v += FH_BLOCK) {
-        const int r = v / vpr, c = (v - r * vpr) * VE;
-        uint4 val = make_uint4(0, 0, 0, 0);
-        if (row0 + r < p.n && c < g.C) val = *reinterpret_cast<const uint4*>(X + (row0 + r) * g.C + c);
-        *reinterpret_cast<uint4*>(bufX + r * lda + c) = val;
-    }
+    stage_rows<DT>(X, row0, p.n, HEAD_ROWS, g.C, Cpad, bufX, lda, false, nullptr, 0, tid);
     __syncthreads();
     const int r = 16 * wave + l16;                     // this lane's row of the tile
     for (int jt = 0; jt < Cpad / 16; ++jt) {
@@ -240,11 +194,10 @@ struct BwdP {
 };
 
 template <int DT>
-__global__ __launch_bounds__(FH_BLOCK) void finehead_backward_kernel(const BwdP p) {
+__global__ __launch_bounds__(HEAD_BLOCK) void finehead_backward_kernel(const BwdP p) {
     using E = typename El<DT>::type;
     using T = Sc<DT>;
     using Acc = typename El<DT>::acc;
-    constexpr int VE = El<DT>::VE;
     extern __shared__ __attribute__((aligned(16))) unsigned char fh_lds[];
     const Geo& g = p.g;
     const int C = g.C, Cpad = g.Cpad, Opad = g.Opad, P = g.P, step = p.step, lda = p.lda, ldz = p.ldz, ldt = p.ldt, rt = step / 16;
@@ -265,38 +218,32 @@ __global__ __launch_bounds__(FH_BLOCK) void finehead_backward_kernel(const BwdP 
     const int64_t r_end = r_begin + p.slab_rows < p.n ? r_begin + p.slab_rows : p.n;
 
     // the weight-gradient tiles of this wave: tile t of [grad_W1 | grad_W2], 16 x 16 each, (out tile, in tile) row-major
-    const int c16 = g.C16 / 16, n1 = c16 * c16, ntiles = n1 + (g.O16 / 16) * c16;
-    const int t_first = (blockIdx.y * 4 + wave) * FH_TPW;
-    Acc accW[FH_TPW];
+    const int c16 = g.C16 / 16, n1 = c16 * c16;
+    WgTiles<DT> wg = {};
+    wg.n = 2; wg.ntiles = n1 + (g.O16 / 16) * c16; wg.C = C; wg.c16 = c16;
+    wg.s[0] = {z1T, xT, 0, C, 0};
+    wg.s[1] = {gT, hT, n1, P, (int64_t)C * C};
+    const int t_first = (blockIdx.y * 4 + wave) * HEAD_TPW;
+    Acc accW[HEAD_TPW];
 #pragma unroll
-    for (int i = 0; i < FH_TPW; ++i) accW[i] = Acc{0, 0, 0, 0};
+    for (int i = 0; i < HEAD_TPW; ++i) accW[i] = Acc{0, 0, 0, 0};
     T db1 = 0, db2 = 0;
 
     // the pad columns of g are never written again
-    for (int i = tid; i < step * (Opad - P); i += FH_BLOCK) {
+    for (int i = tid; i < step * (Opad - P); i += HEAD_BLOCK) {
         const int r = i / (Opad - P), j = P + i - r * (Opad - P);
         RZ[r * ldz + j] = down<DT>(0.0f);
         gT[j * ldt + r] = down<DT>(0.0f);
     }
 
     for (int64_t r0 = r_begin; r0 < r_end; r0 += step) {
-        const int vpr = Cpad / VE;
-        for (int v = tid; v < step * vpr; v += FH_BLOCK) {
-            const int r = v / vpr, c = (v - r * vpr) * VE;
-            union { uint4 v; E e[VE]; } u;
-            u.v = make_uint4(0, 0, 0, 0);
-            if (r0 + r < r_end && c < C) u.v = *reinterpret_cast<const uint4*>(X + (r0 + r) * C + c);
-            *reinterpret_cast<uint4*>(R0 + r * lda + c) = u.v;
-            if (sums)
-#pragma unroll
-                for (int e = 0; e < VE; ++e) xT[(c + e) * ldt + r] = u.e[e];
-        }
+        stage_rows<DT>(X, r0, r_end, step, C, Cpad, R0, lda, sums, xT, ldt, tid);
         // g -> RZ and gT
         {
             const int64_t left = r_end - r0;
             const int count = (int)(left < step ? left : step) * P;
             const int64_t base = r0 * P;
-            for (int i = tid; i < step * P; i += FH_BLOCK) {
+            for (int i = tid; i < step * P; i += HEAD_BLOCK) {
                 const int r = i / P, j = i - r * P;
                 const E e = down<DT>(i < count && p.gout ? load_any(p.gout, base + i, p.gout_dtype) : 0.0f);
                 RZ[r * ldz + j] = e;
@@ -334,30 +281,9 @@ __global__ __launch_bounds__(FH_BLOCK) void finehead_backward_kernel(const BwdP 
         }
         __syncthreads();
         // grad_x = dz1 W1
-        if (p.grad_x && blockIdx.y == 0)
-            for (int pr = wave; pr < (g.C16 / 16) * rt; pr += 4) {
-                const int ti = pr % rt, jt = pr / rt, ch = 16 * jt + 4 * quad;
-                const int64_t row = r0 + 16 * ti + l16;
-                Acc acc = {0, 0, 0, 0};
-                tile_mma<DT>(W1t + (int64_t)16 * jt * Cpad, Cpad, R0 + 16 * ti * lda, lda, Cpad, l16, quad, acc);
-                if (row < r_end && ch < C) {          // C is a multiple of 8: the 4 channels are in or out together
-                    E d[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) d[e] = down<DT>((float)acc[e]);
-                    store4<DT>((E*)p.grad_x + row * C + ch, d);
-                }
-            }
+        if (p.grad_x && blockIdx.y == 0) grad_x_tiles<DT>(W1t, R0, lda, p.grad_x, r0, r_end, rt, C, g.C16, Cpad, wave, l16, quad);
         if (sums) {
-#pragma unroll
-            for (int i = 0; i < FH_TPW; ++i) {
-                int t = t_first + i;
-                if (t >= ntiles) continue;            // (uniform over the wave)
-                const E* A;
-                const E* B;
-                if (t < n1) { A = z1T; B = xT; }
-                else { A = gT; B = hT; t -= n1; }
-                tile_mma<DT>(A + 16 * (t / c16) * ldt, ldt, B + 16 * (t % c16) * ldt, ldt, step, l16, quad, accW[i]);
-            }
+            wgrad_step<DT>(wg, t_first, ldt, step, l16, quad, accW);
             if (blockIdx.y == 0) {
                 if (tid < C)
                     for (int r = 0; r < step; ++r) db1 += (T)up<DT>(z1T[tid * ldt + r]);
@@ -369,60 +295,11 @@ __global__ __launch_bounds__(FH_BLOCK) void finehead_backward_kernel(const BwdP 
     }
     if (!sums) return;
     T* part = (T*)p.part + (int64_t)blockIdx.x * partial_elems(g);
-#pragma unroll
-    for (int i = 0; i < FH_TPW; ++i) {
-        int t = t_first + i;
-        if (t >= ntiles) continue;
-        int64_t base = 0;
-        int olim = C;
-        if (t >= n1) { base = (int64_t)C * C; olim = P; t -= n1; }
-        const int in = 16 * (t % c16) + l16;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int o = 16 * (t / c16) + 4 * quad + e;
-            if (o < olim && in < C) part[base + (int64_t)o * C + in] = accW[i][e];
-        }
-    }
+    wgrad_store<DT>(wg, t_first, part, l16, quad, accW);
     if (blockIdx.y == 0) {
         T* pb = part + (int64_t)C * C + (int64_t)P * C;
         if (tid < C) pb[tid] = db1;
         if (tid < P) pb[C + tid] = db2;
-    }
-}
-
-// the four parameter gradients = the slabs' partial sets added in slab order, each rounded once to its dtype
-struct FoldP {
-    const void* part;
-    void* out[4];              // grad_W1, grad_W2, grad_b1, grad_b2; any may be NULL
-    int32_t out_dtype[4];
-    int64_t size[4];
-    int64_t total;
-    int32_t slabs;
-};
-
-// a block owns FH_FOLD elements; 16 threads per element add one segment of the slabs each, in slab order, then the first adds
-// the 16 segment sums in segment order
-template <typename T>
-__global__ __launch_bounds__(FH_BLOCK) void finehead_fold_kernel(const FoldP p) {
-    __shared__ T sSeg[FH_FOLD][FH_FOLD];
-    const int el = threadIdx.x % FH_FOLD, seg = threadIdx.x / FH_FOLD;
-    int64_t i = (int64_t)blockIdx.x * FH_FOLD + el;
-    const int per = (p.slabs + FH_FOLD - 1) / FH_FOLD, b0 = seg * per, b1 = b0 + per < p.slabs ? b0 + per : p.slabs;
-    T s = 0;
-    if (i < p.total)
-        for (int b = b0; b < b1; ++b) s += ((const T*)p.part)[(int64_t)b * p.total + i];
-    sSeg[seg][el] = s;
-    __syncthreads();
-    if (seg != 0 || i >= p.total) return;
-    T sum = 0;
-    for (int k = 0; k < FH_FOLD; ++k) sum += sSeg[k][el];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (i < p.size[k]) {
-            if (p.out[k]) store_any(p.out[k], i, p.out_dtype[k], (float)sum);
-            return;
-        }
-        i -= p.size[k];
     }
 }
 
@@ -457,18 +334,18 @@ __device__ __forceinline__ int scan_flags(const ScanP& p, int b, int tid, int64_
 __device__ __forceinline__ int block_exclusive(int mine, int tid, int* sScan, int& total) {
     sScan[tid] = mine;
     __syncthreads();
-    for (int d = 1; d < FH_BLOCK; d *= 2) {
+    for (int d = 1; d < HEAD_BLOCK; d *= 2) {
         const int add = tid >= d ? sScan[tid - d] : 0;
         __syncthreads();
         sScan[tid] += add;
         __syncthreads();
     }
-    total = sScan[FH_BLOCK - 1];
+    total = sScan[HEAD_BLOCK - 1];
     return sScan[tid] - mine;
 }
 
-__global__ __launch_bounds__(FH_BLOCK) void finehead_scan_count_kernel(const ScanP p) {
-    __shared__ int sScan[FH_BLOCK];
+__global__ __launch_bounds__(HEAD_BLOCK) void finehead_scan_count_kernel(const ScanP p) {
+    __shared__ int sScan[HEAD_BLOCK];
     int64_t row0;
     int total;
     block_exclusive(__popc(scan_flags(p, blockIdx.x, threadIdx.x, row0)), threadIdx.x, sScan, total);
@@ -476,12 +353,12 @@ __global__ __launch_bounds__(FH_BLOCK) void finehead_scan_count_kernel(const Sca
 }
 
 // one block: the exclusive scan of each side's chunk counts, in place, and the two totals
-__global__ __launch_bounds__(FH_BLOCK) void finehead_scan_bases_kernel(const ScanP p) {
-    __shared__ int sScan[FH_BLOCK];
+__global__ __launch_bounds__(HEAD_BLOCK) void finehead_scan_bases_kernel(const ScanP p) {
+    __shared__ int sScan[HEAD_BLOCK];
     const int tid = threadIdx.x;
     for (int side = 0; side < 2; ++side) {
         int32_t* c = p.counts + (side ? p.chunksA : 0);
-        const int n = side ? p.chunksB : p.chunksA, per = (n + FH_BLOCK - 1) / FH_BLOCK;
+        const int n = side ? p.chunksB : p.chunksA, per = (n + HEAD_BLOCK - 1) / HEAD_BLOCK;
         const int b0 = tid * per < n ? tid * per : n, b1 = b0 + per < n ? b0 + per : n;
         int mine = 0, total;
         for (int b = b0; b < b1; ++b) mine += c[b];
@@ -496,8 +373,8 @@ __global__ __launch_bounds__(FH_BLOCK) void finehead_scan_bases_kernel(const Sca
     }
 }
 
-__global__ __launch_bounds__(FH_BLOCK) void finehead_scan_write_kernel(const ScanP p) {
-    __shared__ int sScan[FH_BLOCK];
+__global__ __launch_bounds__(HEAD_BLOCK) void finehead_scan_write_kernel(const ScanP p) {
+    __shared__ int sScan[HEAD_BLOCK];
     const int b = blockIdx.x, tid = threadIdx.x;
     const bool sideA = b < p.chunksA;
     int64_t row0;
@@ -558,9 +435,9 @@ __device__ __forceinline__ float assembled(const AsmP& p, int k, int w, int64_t 
     return p.coarse[k][i * w + col];
 }
 
-__global__ __launch_bounds__(FH_BLOCK) void finehead_assemble_kernel(const AsmP p) {
-    const int64_t stride = (int64_t)gridDim.x * FH_BLOCK;
-    for (int64_t gi = (int64_t)blockIdx.x * FH_BLOCK + threadIdx.x; gi < p.groups_end[4]; gi += stride) {
+__global__ __launch_bounds__(HEAD_BLOCK) void finehead_assemble_kernel(const AsmP p) {
+    const int64_t stride = (int64_t)gridDim.x * HEAD_BLOCK;
+    for (int64_t gi = (int64_t)blockIdx.x * HEAD_BLOCK + threadIdx.x; gi < p.groups_end[4]; gi += stride) {
         int k = 0;
         while (gi >= p.groups_end[k]) ++k;
         const int w = width_of(k, p.sh);
@@ -595,9 +472,9 @@ __device__ __forceinline__ int64_t survivor_of(const AsmBwdP& p, int64_t m) {
     return j >= 0 && j < p.n_rest ? p.start[p.n_levels] + j : -1;
 }
 
-__global__ __launch_bounds__(FH_BLOCK) void finehead_assemble_backward_kernel(const AsmBwdP p) {
-    const int64_t stride = (int64_t)gridDim.x * FH_BLOCK;
-    for (int64_t t = (int64_t)blockIdx.x * FH_BLOCK + threadIdx.x; t < p.ends[6]; t += stride) {
+__global__ __launch_bounds__(HEAD_BLOCK) void finehead_assemble_backward_kernel(const AsmBwdP p) {
+    const int64_t stride = (int64_t)gridDim.x * HEAD_BLOCK;
+    for (int64_t t = (int64_t)blockIdx.x * HEAD_BLOCK + threadIdx.x; t < p.ends[6]; t += stride) {
         int s = 0;
         while (t >= p.ends[s]) ++s;
         const int64_t e = t - (s ? p.ends[s - 1] : 0);
@@ -629,69 +506,30 @@ __global__ __launch_bounds__(FH_BLOCK) void finehead_assemble_backward_kernel(co
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-size_t esize(int dtype) { return dtype == GDR_NORM_F32 ? 4 : 2; }
-
 bool bad_sh(int32_t sh) { return sh != 3 && sh != 12 && sh != 27 && sh != 48; }
 bool bad_shape(int32_t C, int32_t sh) { return C < 8 || C > GDR_FINEHEAD_MAX_C || C % 8 || bad_sh(sh); }
 bool bad_rows_count(int64_t rows) { return rows > (INT64_C(1) << 31) - 1; }
 
 const char* const FH_ENVELOPE = "finehead: C must be a multiple of 8 in 8..GDR_FINEHEAD_MAX_C, sh_dim one of 3, 12, 27, 48 and rows below 2^31";
 
-int slabs_of(int64_t n) {
-    const int64_t s = (n + FH_SLAB_MIN - 1) / FH_SLAB_MIN;
-    return s < 1 ? 1 : (s > FH_MAX_SLABS ? FH_MAX_SLABS : (int)s);
-}
+int slabs_of(int64_t n) { return slabs_of(n, FH_SLAB_MIN, FH_MAX_SLABS); }
 
 struct FwdLds { int lda; size_t total; };
 FwdLds fwd_lds(int dtype, const Geo& g) {
     FwdLds l;
     l.lda = g.Cpad + (dtype == GDR_NORM_F32 ? 4 : 8);
-    l.total = (size_t)2 * FH_ROWS * l.lda * esize(dtype);
+    l.total = (size_t)2 * HEAD_ROWS * l.lda * esize(dtype);
     return l;
 }
 
-struct BwdLds { int step, lda, ldz, ldt; size_t total; };
-size_t bwd_bytes(int dtype, const Geo& g, int step, BwdLds* l) {
-    const int ve = dtype == GDR_NORM_F32 ? 4 : 8;
-    l->step = step; l->lda = g.Cpad + ve; l->ldz = g.Opad + ve; l->ldt = step + ve;
-    l->total = esize(dtype) * ((size_t)2 * step * l->lda + (size_t)step * l->ldz + (size_t)(3 * g.Cpad + g.Opad) * l->ldt);
-    return l->total;
-}
-// the rows per step: the most that leave room for two workgroups per CU, or else the fewest
-BwdLds bwd_lds(int dtype, const Geo& g) {
-    BwdLds l;
-    const int least = dtype == GDR_NORM_F32 ? 16 : 32;
-    for (int step = 64; step > least; step /= 2)
-        if (bwd_bytes(dtype, g, step, &l) <= FH_LDS_PREFER) return l;
-    bwd_bytes(dtype, g, least, &l);
-    return l;
-}
-
-template <typename K> hipError_t allow_lds(K kernel, size_t bytes) {
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-#define GDR_FINEHEAD_DT(KERNEL, GRID, LDS, ST, P)                                                                          \
-    do {                                                                                                                   \
-        hipError_t e_;                                                                                                     \
-        if (dtype == GDR_NORM_F16) {                                                                                       \
-            if ((e_ = allow_lds(KERNEL<GDR_NORM_F16>, LDS)) != hipSuccess) { set_error(#KERNEL, e_); return GDR_ERR_HIP; } \
-            hipLaunchKernelGGL(KERNEL<GDR_NORM_F16>, GRID, dim3(FH_BLOCK), LDS, ST, P);                                    \
-        } else if (dtype == GDR_NORM_BF16) {                                                                               \
-            if ((e_ = allow_lds(KERNEL<GDR_NORM_BF16>, LDS)) != hipSuccess) { set_error(#KERNEL, e_); return GDR_ERR_HIP; } \
-            hipLaunchKernelGGL(KERNEL<GDR_NORM_BF16>, GRID, dim3(FH_BLOCK), LDS, ST, P);                                   \
-        } else {                                                                                                           \
-            if ((e_ = allow_lds(KERNEL<GDR_NORM_F32>, LDS)) != hipSuccess) { set_error(#KERNEL, e_); return GDR_ERR_HIP; } \
-            hipLaunchKernelGGL(KERNEL<GDR_NORM_F32>, GRID, dim3(FH_BLOCK), LDS, ST, P);                                    \
-        }                                                                                                                  \
-    } while (0)
+// the backward's steps: xT, hT and z1T are its transposed Cpad-channel buffers
+BwdLds bwd_lds(int dtype, const Geo& g) { return bwd_lds(dtype, g.Cpad, g.Opad, 3); }
 
 int chunks_of(int64_t n) { return (int)((n + FH_CHUNK - 1) / FH_CHUNK); }
 
 // the grid of an elementwise kernel that strides: enough blocks for `items`, 4096 at most
 dim3 strided_grid(int64_t items) {
-    const int64_t blocks = (items + FH_BLOCK - 1) / FH_BLOCK;
+    const int64_t blocks = (items + HEAD_BLOCK - 1) / HEAD_BLOCK;
     return dim3((uint32_t)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks)));
 }
 
@@ -743,10 +581,10 @@ int gdr_finehead_pack(const void* w1, int32_t w1_dtype, const void* w2, int32_t 
     PackP p = {};
     p.w[0] = w1; p.w[1] = w2; p.w_dtype[0] = w1_dtype; p.w_dtype[1] = w2_dtype;
     p.packed = packed; p.g = geo_of(dtype, C, sh_dim); p.backward = backward ? 1 : 0; p.total = packed_elems(p.g, backward != 0);
-    const dim3 grid((uint32_t)div_up(p.total, (int64_t)FH_BLOCK));
-    if (dtype == GDR_NORM_F16) hipLaunchKernelGGL(finehead_pack_kernel<GDR_NORM_F16>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, p);
-    else if (dtype == GDR_NORM_BF16) hipLaunchKernelGGL(finehead_pack_kernel<GDR_NORM_BF16>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(finehead_pack_kernel<GDR_NORM_F32>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, p);
+    const dim3 grid((uint32_t)div_up(p.total, (int64_t)HEAD_BLOCK));
+    if (dtype == GDR_NORM_F16) hipLaunchKernelGGL(finehead_pack_kernel<GDR_NORM_F16>, grid, dim3(HEAD_BLOCK), 0, (hipStream_t)stream, p);
+    else if (dtype == GDR_NORM_BF16) hipLaunchKernelGGL(finehead_pack_kernel<GDR_NORM_BF16>, grid, dim3(HEAD_BLOCK), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(finehead_pack_kernel<GDR_NORM_F32>, grid, dim3(HEAD_BLOCK), 0, (hipStream_t)stream, p);
     return launch_status("finehead_pack_kernel");
 }
 
@@ -765,9 +603,9 @@ int gdr_finehead_forward(const void* x, int32_t dtype, const void* packed, const
     p.x = x; p.packed = packed; p.b[0] = b1; p.b[1] = b2; p.b_dtype[0] = b1_dtype; p.b_dtype[1] = b2_dtype;
     p.out = out; p.out_dtype = out_dtype; p.n = rows; p.g = geo_of(dtype, C, sh_dim);
     const FwdLds l = fwd_lds(dtype, p.g);
-    if (l.total > FH_LDS_MAX) return unsupported("finehead_forward: the tile does not fit LDS");
+    if (l.total > HEAD_LDS_MAX) return unsupported("finehead_forward: the tile does not fit LDS");
     p.lda = l.lda;
-    GDR_FINEHEAD_DT(finehead_forward_kernel, dim3((uint32_t)div_up(rows, (int64_t)FH_ROWS)), l.total, (hipStream_t)stream, p);
+    GDR_HEAD_DT(finehead_forward_kernel, dim3((uint32_t)div_up(rows, (int64_t)HEAD_ROWS)), l.total, (hipStream_t)stream, p);
     return launch_status("finehead_forward_kernel");
 }
 
@@ -788,42 +626,32 @@ int gdr_finehead_backward(const void* x, int32_t dtype, const void* packed, cons
     p.x = x; p.packed = packed; p.b1 = b1; p.b1_dtype = b1_dtype; p.gout = grad_out; p.gout_dtype = grad_out ? grad_out_dtype : dtype;
     p.grad_x = grad_x; p.part = workspace; p.n = rows; p.g = geo_of(dtype, C, sh_dim);
     const BwdLds l = bwd_lds(dtype, p.g);
-    if (l.total > FH_LDS_MAX) return unsupported("finehead_backward: the step does not fit LDS");
+    if (l.total > HEAD_LDS_MAX) return unsupported("finehead_backward: the step does not fit LDS");
     p.step = l.step; p.lda = l.lda; p.ldz = l.ldz; p.ldt = l.ldt;
     const int slabs = slabs_of(rows);
-    p.slab_rows = (int64_t)align_up((size_t)((rows + slabs - 1) / slabs), FH_ROWS);
+    p.slab_rows = (int64_t)align_up((size_t)((rows + slabs - 1) / slabs), HEAD_ROWS);
     const int c16 = p.g.C16 / 16, ntiles = c16 * c16 + (p.g.O16 / 16) * c16;
-    const int groups = workspace ? div_up(ntiles, 4 * FH_TPW) : 1;
-    GDR_FINEHEAD_DT(finehead_backward_kernel, dim3(slabs, groups), l.total, (hipStream_t)stream, p);
+    const int groups = workspace ? div_up(ntiles, 4 * HEAD_TPW) : 1;
+    GDR_HEAD_DT(finehead_backward_kernel, dim3(slabs, groups), l.total, (hipStream_t)stream, p);
     return launch_status("finehead_backward_kernel");
 }
 
 int gdr_finehead_fold(const void* workspace, size_t workspace_bytes, int32_t dtype, int64_t rows, int32_t C, int32_t sh_dim, void* grad_w1,
                       int32_t grad_w1_dtype, void* grad_b1, int32_t grad_b1_dtype, void* grad_w2, int32_t grad_w2_dtype, void* grad_b2,
                       int32_t grad_b2_dtype, void* stream) {
-    void* out[4] = {grad_w1, grad_w2, grad_b1, grad_b2};
+    FoldP p = {};                  // in the order of a partial set
+    p.count = 4;
+    void* const out[4] = {grad_w1, grad_w2, grad_b1, grad_b2};
     const int32_t dts[4] = {grad_w1_dtype, grad_w2_dtype, grad_b1_dtype, grad_b2_dtype};
-    if (bad_dtype(dtype)) return invalid_arg("finehead_fold: unknown dtype");
-    for (int k = 0; k < 4; ++k)
-        if (out[k] && bad_dtype(dts[k])) return invalid_arg("finehead_fold: unknown dtype");
+    for (int k = 0; k < 4; ++k) { p.out[k] = out[k]; p.out_dtype[k] = dts[k]; }
+    if (fold_bad_dtype(dtype, p)) return invalid_arg("finehead_fold: unknown dtype");
     if (rows < 0) return invalid_arg("finehead_fold: rows must be >= 0");
     if (bad_shape(C, sh_dim) || bad_rows_count(rows)) return unsupported(FH_ENVELOPE);
-    if (!workspace) return invalid_arg("finehead_fold: NULL workspace");
-    if (misaligned(workspace, 255)) return unsupported("finehead_fold: the workspace must start on 256 bytes");
-    for (int k = 0; k < 4; ++k)
-        if (out[k] && misaligned(out[k], esize(dts[k]) - 1)) return unsupported("finehead_fold: a gradient must be aligned to its element");
-    if (workspace_bytes < gdr_finehead_workspace_bytes(GDR_FINEHEAD_WS_PARTIALS, dtype, rows, C, sh_dim))
-        return workspace_too_small("finehead_fold: workspace smaller than gdr_finehead_workspace_bytes");
     const Geo g = geo_of(dtype, C, sh_dim);
-    FoldP p = {};
-    p.part = workspace;
-    for (int k = 0; k < 4; ++k) { p.out[k] = out[k]; p.out_dtype[k] = dts[k]; }
     p.size[0] = (int64_t)C * C; p.size[1] = (int64_t)g.P * C; p.size[2] = C; p.size[3] = g.P;
-    p.total = partial_elems(g); p.slabs = slabs_of(rows);
-    const dim3 grid((uint32_t)div_up(p.total, (int64_t)FH_FOLD));
-    if (dtype == GDR_NORM_F32) hipLaunchKernelGGL(finehead_fold_kernel<double>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(finehead_fold_kernel<float>, grid, dim3(FH_BLOCK), 0, (hipStream_t)stream, p);
-    return launch_status("finehead_fold_kernel");
+    p.slabs = slabs_of(rows);
+    return head_fold("finehead", workspace, workspace_bytes, gdr_finehead_workspace_bytes(GDR_FINEHEAD_WS_PARTIALS, dtype, rows, C, sh_dim), dtype, p,
+                     stream);
 }
 
 size_t gdr_finehead_scan_bytes(int64_t Nc, int64_t n_masked) {
@@ -848,9 +676,9 @@ int gdr_finehead_scan(const uint8_t* mask, int64_t Nc, const uint8_t* selected, 
     p.masked_of_rest = masked_of_rest; p.count = count;
     const int chunks = p.chunksA + p.chunksB;
     hipStream_t st = (hipStream_t)stream;
-    if (chunks) hipLaunchKernelGGL(finehead_scan_count_kernel, dim3(chunks), dim3(FH_BLOCK), 0, st, p);
-    hipLaunchKernelGGL(finehead_scan_bases_kernel, dim3(1), dim3(FH_BLOCK), 0, st, p);
-    if (chunks) hipLaunchKernelGGL(finehead_scan_write_kernel, dim3(chunks), dim3(FH_BLOCK), 0, st, p);
+    if (chunks) hipLaunchKernelGGL(finehead_scan_count_kernel, dim3(chunks), dim3(HEAD_BLOCK), 0, st, p);
+    hipLaunchKernelGGL(finehead_scan_bases_kernel, dim3(1), dim3(HEAD_BLOCK), 0, st, p);
+    if (chunks) hipLaunchKernelGGL(finehead_scan_write_kernel, dim3(chunks), dim3(HEAD_BLOCK), 0, st, p);
     return launch_status("finehead scan kernels");
 }
 
@@ -895,7 +723,7 @@ int gdr_finehead_assemble(int32_t n_levels, const void* const* coord, const void
     const int widths[5] = {3, sh_dim, 1, 3, 4};
     int64_t end = 0;
     for (int k = 0; k < 5; ++k) p.groups_end[k] = end += (p.T * widths[k] + p.vw - 1) / p.vw;
-    hipLaunchKernelGGL(finehead_assemble_kernel, strided_grid(end), dim3(FH_BLOCK), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(finehead_assemble_kernel, strided_grid(end), dim3(HEAD_BLOCK), 0, (hipStream_t)stream, p);
     return launch_status("finehead_assemble_kernel");
 }
 
@@ -940,7 +768,7 @@ int gdr_finehead_assemble_backward(int32_t n_levels, const int64_t* level_rows, 
     p.ends[5] = end += gc[4] ? Nc * 4 : 0;
     p.ends[6] = end += grad_shs_fine ? n_masked * sh_dim : 0;
     if (end == 0) return GDR_OK;
-    hipLaunchKernelGGL(finehead_assemble_backward_kernel, strided_grid(end), dim3(FH_BLOCK), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(finehead_assemble_backward_kernel, strided_grid(end), dim3(HEAD_BLOCK), 0, (hipStream_t)stream, p);
     return launch_status("finehead_assemble_backward_kernel");
 }
 

@@ -36,6 +36,7 @@ static inline bool misaligned(const void* p, unsigned mask) { return ((uintptr_t
 
 // a storage type code of the row kernels (GDR_NORM_F16 / BF16 / F32)
 static inline bool bad_dtype(int32_t dt) { return dt < GDR_NORM_F16 || dt > GDR_NORM_F32; }
+static inline size_t esize(int32_t dt) { return dt == GDR_NORM_F32 ? 4 : 2; }      // the bytes of one element
 
 // a (rows, C) matrix read or written in 8-element pieces: 16-byte base, a stride that is a multiple of 8 and at least C
 static inline bool bad_rows(const void* ptr, int64_t stride, int64_t C) { return misaligned(ptr, 15) || stride < C || stride % 8; }

@@ -1,6 +1,7 @@
-// mfma_rows.h — what the dense row-GEMM kernels (conv3d.hip, deconv3d.hip) share on the device (internal): the storage type
-// of a compute dtype, its conversions, loads and stores of a buffer whose type is only known at run time, and one 16 x 16
-// MFMA step over the sum elements of a 64-byte LDS row pair.  Include after gdr_common.h and half_bits.h.
+// mfma_rows.h — what the dense row-GEMM kernels (conv3d.hip, deconv3d.hip, coarsehead.hip, finehead.hip) share on the device
+// (internal): the storage type of a compute dtype, its conversions, loads and stores of a buffer whose type is only known at
+// run time, and one 16 x 16 MFMA step over the sum elements of a 64-byte LDS row pair.  What only the two heads share sits on
+// top of this in head_rows.h.  Include after gdr_common.h and half_bits.h.
 #pragma once
 #include <type_traits>
 

@@ -427,7 +427,7 @@ const char* subm_check(const gdr_subm_args* a) {
     return nullptr;
 }
 
-size_t esize(int dtype) { return dtype == GDR_SUBM_F32 ? 4 : 2; }
+size_t subm_esize(int dtype) { return dtype == GDR_SUBM_F32 ? 4 : 2; }
 int planes_of(int dtype) { return dtype == GDR_SUBM_F32 ? 1 : (dtype == GDR_SUBM_F16 ? 2 : 3); }
 
 struct BwdWs { size_t G, wt, part, bytes; };
@@ -435,15 +435,15 @@ struct BwdWs { size_t G, wt, part, bytes; };
 BwdWs bwd_workspace(const gdr_subm_args* a) {
     BwdWs w;
     size_t at = 0;
-    w.G = at; at += align_up((size_t)planes_of(a->dtype) * (size_t)a->N * a->Cout * esize(a->dtype));
-    w.wt = at; at += align_up((size_t)a->K * a->Cin * a->Cout * esize(a->dtype));
+    w.G = at; at += align_up((size_t)planes_of(a->dtype) * (size_t)a->N * a->Cout * subm_esize(a->dtype));
+    w.wt = at; at += align_up((size_t)a->K * a->Cin * a->Cout * subm_esize(a->dtype));
     w.part = at; at += align_up((size_t)SC_BIAS_BLOCKS * a->Cout * sizeof(float));
     w.bytes = at;
     return w;
 }
 
 int row_vec(const void* ptr, int64_t stride, int dtype) {
-    return !((uintptr_t)ptr & 15u) && (stride * (int64_t)esize(dtype)) % 16 == 0;
+    return !((uintptr_t)ptr & 15u) && (stride * (int64_t)subm_esize(dtype)) % 16 == 0;
 }
 
 #define GDR_SUBM_DT(KERNEL, ...)                                                                          \
@@ -526,7 +526,7 @@ int gdr_subm_conv_forward(const gdr_subm_args* a, const void* feat, int64_t feat
     if (a->N == 0) return GDR_OK;
     if (!feat || !nbr || !weight || !out) return invalid_arg("subm_conv_forward: NULL argument");
     if (feat_stride < a->Cin) return invalid_arg("subm_conv_forward: feature row stride smaller than Cin");
-    const size_t es = esize(a->dtype);
+    const size_t es = subm_esize(a->dtype);
     if (misaligned(feat, es - 1) || misaligned(bias, es - 1) || misaligned(weight, 15) || misaligned(out, 15) ||
         misaligned(nbr, 3))
         return invalid_arg("subm_conv_forward: unaligned buffer");
@@ -549,7 +549,7 @@ int gdr_subm_conv_backward(const gdr_subm_args* a, const void* grad_out, const v
     if (const char* why = subm_check(a)) return invalid_arg(why);
     if (a->N == 0) return GDR_OK;
     if (!grad_feat && !grad_weight && !grad_bias) return GDR_OK;
-    const size_t es = esize(a->dtype);
+    const size_t es = subm_esize(a->dtype);
     if (!grad_out || misaligned(grad_out, 15)) return invalid_arg("subm_conv_backward: grad_out NULL or unaligned");
     const hipStream_t st = (hipStream_t)stream;
     const BwdWs ws = bwd_workspace(a);

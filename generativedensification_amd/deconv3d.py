@@ -56,8 +56,8 @@ GRAD_WEIGHT_SLAB_ROWS = L.GDR_DECONV3D_SLAB_MIN       # the weight gradient cuts
 # reference's four lines, on purpose: the A/B of scripts/bench_deconv3d.py)
 TAIL_BACKEND = "hip"
 
-_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-           torch.float32: L.GDR_NORM_DTYPES["f32"]}
+_DTYPES = M.NORM_DTYPES
+_dense = M.dense
 _NO_CPU = "the HIP transposed convolution runs on ROCm/HIP tensors only (no CPU fallback)"
 
 
@@ -70,19 +70,11 @@ def in_envelope(B, Cin, Cout, D, H, W):
 def _rows(x):
     """x (B, C, D, H, W) as its (B, D, H, W, C) rows, dense from a 16-byte aligned base: a view of a channels_last_3d x (the
     strides of size-1 axes do not count), one copy of anything else"""
-    rows = x.permute(0, 2, 3, 4, 1)
-    if rows.numel() and (not rows.is_contiguous() or rows.data_ptr() % 16):
-        rows = rows.contiguous()
-        if rows.data_ptr() % 16:
-            rows = rows.clone()
-    return rows
+    return M.dense_aligned(x.permute(0, 2, 3, 4, 1))
 
 
 def _workspace(lib, what, dt, rows, cin, cout, dev):
-    nbytes = lib.gdr_deconv3d_workspace_bytes(what, dt, rows, cin, cout)
-    if nbytes == 0:
-        L.check(-1, "gdr_deconv3d_workspace_bytes")
-    return M.workspace(nbytes + 256, dev)
+    return M.queried_workspace(lib.gdr_deconv3d_workspace_bytes, "gdr_deconv3d_workspace_bytes", dev, what, dt, rows, cin, cout)
 
 
 def _dt(t, default):
@@ -95,10 +87,6 @@ def _packed(lib, w, transposed, dt, dev):
     L.check(lib.gdr_deconv3d_pack_weight(w.data_ptr(), _DTYPES[w.dtype], cin, cout, int(transposed), base, dt, M.stream()),
             "gdr_deconv3d_pack_weight")
     return ws, base
-
-
-def _dense(t):
-    return t if t is None or t.is_contiguous() else t.contiguous()
 
 
 class _Deconv(torch.autograd.Function):

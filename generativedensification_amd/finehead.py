@@ -71,8 +71,8 @@ SH_DIMS = (3, 12, 27, 48)
 # the project's rule ships "hip" only where it measured faster.  gaussian_head itself always runs the kernels.
 HEAD_BACKEND = "torch"
 
-_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-           torch.float32: L.GDR_NORM_DTYPES["f32"]}
+_DTYPES = M.NORM_DTYPES
+_dense = M.dense
 _NO_CPU = "the HIP fine head runs on ROCm/HIP tensors only (no CPU fallback)"
 
 
@@ -89,24 +89,13 @@ def backward_step(dtype, C, sh_dim):
     return step
 
 
-def _dense(t):
-    return t if t is None or t.is_contiguous() else t.contiguous()
-
-
 def _rows(x):
     """x (N, C) dense from a 16-byte aligned base: x itself where it is so already, one copy otherwise"""
-    if x.numel() and (not x.is_contiguous() or x.data_ptr() % 16):
-        x = x.contiguous()
-        if x.data_ptr() % 16:
-            x = x.clone()
-    return x
+    return M.dense_aligned(x)
 
 
 def _workspace(lib, what, dt, rows, C, sh_dim, dev):
-    nbytes = lib.gdr_finehead_workspace_bytes(what, dt, rows, C, sh_dim)
-    if nbytes == 0:
-        L.check(-1, "gdr_finehead_workspace_bytes")
-    return M.workspace(nbytes + 256, dev)
+    return M.queried_workspace(lib.gdr_finehead_workspace_bytes, "gdr_finehead_workspace_bytes", dev, what, dt, rows, C, sh_dim)
 
 
 def _packed(lib, w1, w2, backward, dt, C, sh_dim, dev):
