@@ -200,6 +200,13 @@ GDR_FINEHEAD_MAX_C, GDR_FINEHEAD_TILE_ROWS, GDR_FINEHEAD_SLAB_MIN, GDR_FINEHEAD_
 GDR_FINEHEAD_WS_PACKED_FORWARD, GDR_FINEHEAD_WS_PACKED_BACKWARD, GDR_FINEHEAD_WS_PARTIALS = 0, 1, 2
 
 
+GDR_VOLCOND_SLAB_ROWS, GDR_VOLCOND_MAX_CHANNELS, GDR_VOLCOND_MAX_SIDE, GDR_VOLCOND_MAX_ENTRIES = 32, 4096, 1024, 1 << 30
+
+
+class GdrVolcondSampleArgs(C.Structure):   # include/gdr.h gdr_volcond_sample_args
+    _fields_ = [(name, C.c_int32) for name in ("B", "V", "h", "w", "C", "E", "r", "n_group", "img_h", "img_w")]
+
+
 GDR_DENSIFY_MODES = {"top_k": 0, "top_p": 1}
 GDR_DENSIFY_MAX_SEGMENTS, GDR_DENSIFY_MAX_CHANNELS, GDR_DENSIFY_CHUNK = 1024, 1024, 1024
 
@@ -441,6 +448,18 @@ _PROTOS = {
                               [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double] + [C.c_void_p] * 6),
     "gdr_finehead_assemble_backward": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_int64] * 3 +
                                        [C.c_void_p] * 8),
+    "gdr_volcond_ray_sh": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gdr_volcond_modln_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p, C.c_int32] * 2 +
+                                  [C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_volcond_modln_backward_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gdr_volcond_modln_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                            C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p, C.c_int32] * 2 +
+                                   [C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5),
+    "gdr_volcond_sample_forward": (C.c_int, [C.POINTER(GdrVolcondSampleArgs), C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
+                                   [C.c_int64, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 3),
+    "gdr_volcond_sample_backward_bytes": (C.c_size_t, [C.POINTER(GdrVolcondSampleArgs)]),
+    "gdr_volcond_sample_backward": (C.c_int, [C.POINTER(GdrVolcondSampleArgs), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "gdr_profile_enable": (C.c_int, [C.c_int]),
     "gdr_profile_collect": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32, C.c_int32]),
     "gdr_kernel_count": (C.c_int, []),

@@ -11,6 +11,7 @@ one contiguous C-element row: what the bound blocks (groupattn.py, conv3d.py) ha
     in_envelope(B, Cin, Cout, D, H, W)                         whether the kernels serve this shape
     vol_transformer_forward(self, image_feats)                 VolTransformer.forward with this tail; bound with one line,
                                                                network.VolTransformer.forward = deconv3d.vol_transformer_forward
+    vol_transformer_forward_from_conds(self, conds, B)         the same behind its cond line, from the conds of volcond.volume_conds
 
 x is (B, Cin, D, H, W), weight (Cin, Cout, 2, 2, 2) in nn.ConvTranspose3d's own layout, bias (Cout,) or None; the result is
 (B, Cout, 2D, 2H, 2W) with dense channels_last_3d strides, so `out.permute(0, 2, 3, 4, 1)` is the reference's contiguous
@@ -44,8 +45,8 @@ import torch
 from . import _lib as L
 from . import _marshal as M
 
-__all__ = ["conv_transpose3d_2x", "conv_transpose3d_2x_of", "covers", "in_envelope", "vol_transformer_forward", "TAIL_BACKEND",
-           "MAX_CIN", "MAX_COUT", "MAX_ROWS", "TILE_ROWS", "GRAD_WEIGHT_SLAB_ROWS"]
+__all__ = ["conv_transpose3d_2x", "conv_transpose3d_2x_of", "covers", "in_envelope", "vol_transformer_forward",
+           "vol_transformer_forward_from_conds", "TAIL_BACKEND", "MAX_CIN", "MAX_COUT", "MAX_ROWS", "TILE_ROWS", "GRAD_WEIGHT_SLAB_ROWS"]
 
 MAX_CIN, MAX_COUT = L.GDR_DECONV3D_MAX_CIN, L.GDR_DECONV3D_MAX_COUT
 MAX_ROWS = ((1 << 31) - 1) // 8     # parent voxels
@@ -263,6 +264,28 @@ def vol_transformer_forward(self, image_feats):
         raise ValueError(f"deconv3d.TAIL_BACKEND must be 'torch' or 'hip', not {TAIL_BACKEND!r}")
     B, V, C, D, H, W = image_feats.shape
     volume_feats = [_cond(image_feats, n_group, D // n_group) for n_group in self.n_groups]
+    # the rows (B, d, h, w, E) of pos_embed repeated over the batch, one copy; seen as (B, E, d, h, w)
+    x = self.pos_embed.expand(B, -1, -1, -1, -1).permute(0, 2, 3, 4, 1).clone(memory_format=torch.contiguous_format).permute(0, 4, 1, 2, 3)
+    for i, layer in enumerate(self.layers):
+        group_idx = i % len(self.block_size)
+        x = layer(x, volume_feats[group_idx], self.n_groups[group_idx], self.block_size[group_idx])
+    if (TAIL_BACKEND == "hip" and covers(self.deconv, self.norm)
+            and in_envelope(x.shape[0], self.deconv.in_channels, self.deconv.out_channels, *x.shape[2:])):
+        return conv_transpose3d_2x_of(self.deconv, x, self.norm).permute(0, 2, 3, 4, 1)
+    x = self.norm(torch.einsum('bcdhw->bdhwc', x))
+    x = torch.einsum('bdhwc->bcdhw', x)
+    x_up = self.deconv(x)
+    return torch.einsum('bcdhw->bdhwc', x_up).contiguous()
+
+
+def vol_transformer_forward_from_conds(self, conds, B):
+    """vol_transformer_forward behind its cond line (the same lines, restated: that function stays as it is): `conds` holds one
+    (B g^3, V bs^3, C) cond per entry of self.n_groups (what volcond.volume_conds returns) and B is the batch size."""
+    if TAIL_BACKEND not in ("torch", "hip"):
+        raise ValueError(f"deconv3d.TAIL_BACKEND must be 'torch' or 'hip', not {TAIL_BACKEND!r}")
+    volume_feats = list(conds)
+    if len(volume_feats) != len(self.n_groups):
+        raise ValueError(f"{len(self.n_groups)} group sizes need as many conds, got {len(volume_feats)}")
     # the rows (B, d, h, w, E) of pos_embed repeated over the batch, one copy; seen as (B, E, d, h, w)
     x = self.pos_embed.expand(B, -1, -1, -1, -1).permute(0, 2, 3, 4, 1).clone(memory_format=torch.contiguous_format).permute(0, 4, 1, 2, 3)
     for i, layer in enumerate(self.layers):

@@ -1225,6 +1225,60 @@ int gdr_finehead_assemble_backward(int32_t n_levels, const int64_t* level_rows, 
                                    void* const* grad_coord, void* const* grad_attr, void* grad_centers_coarse, void* grad_opacity_coarse,
                                    void* grad_scaling_coarse, void* grad_rotation_coarse, void* grad_shs_fine, void* stream);
 
+/* ---- volume conditioning of the volume transformer (csrc/volcond.hip; added in v17, backward-compatible) -------------------
+ * What the reference computes between its image encoder and the first GroupAttBlock (Network.build_feat_vol, the view_embed
+ * concat of Network.forward, the cond regrouping of VolTransformer.forward): the spherical-harmonics embedding of the Pluecker
+ * rays, the modulated LayerNorm of the token rows, and the projected bilinear sampling of the token maps written straight into
+ * the (B g^3, V bs^3, C + E) cond of the blocks.  The arithmetic is restated in the header of csrc/volcond.hip.  The caller owns
+ * every buffer; all are device memory except `a`.  Every `*_dtype` is one of GDR_NORM_F16 / BF16 / F32 and the types of one call
+ * are independent; the arithmetic is f32.  Refusals happen before any launch; no entry point allocates or synchronises with the
+ * host.  No atomics: two runs are bitwise equal.  "rows of X" means a 16-byte aligned base and a row stride (elements) that is a
+ * multiple of 8 and covers the row.
+ *
+ * ray_sh: rays (n, 6) dense of rays_dtype -> out (n, 32) dense f32, 16-byte aligned; silu != 0 applies SiLU.  1 launch.
+ * modln_forward: rows of x (R, C), row o * x_inner + i at element o * x_outer_stride + i * x_stride (a token map read where the
+ *   encoder left it; x_outer_stride a multiple of 8; x_inner >= R and x_outer_stride 0 for a plain matrix); rows of shift_scale (R, 2 C), shift in [:, :C], scale in [:, C:]; weight, bias: C dense
+ *   elements, 16-byte aligned, or NULL (1 and 0); out (R, C) dense, 16-byte aligned.  C a multiple of 8 in
+ *   8..GDR_NORM_MAX_CHANNELS, R below 2^31; R = 0 returns GDR_OK without a launch.  1 launch.
+ * modln_backward: grad_out: rows of (R, C) of grad_dtype.  grad_x (R, C) dense of x_dtype, grad_shift_scale (R, 2 C) dense of
+ *   ss_dtype, both 16-byte aligned; grad_weight, grad_bias: C elements of weight_dtype / bias_dtype.  A NULL output is not
+ *   wanted and not computed.  The row statistics are recomputed.  workspace (only with grad_weight or grad_bias):
+ *   gdr_volcond_modln_backward_bytes(R, C) bytes, 256-byte aligned: one partial pair per GDR_VOLCOND_SLAB_ROWS rows, folded in
+ *   ascending order by the second launch.  1 launch, 2 with a parameter gradient.
+ * sample_forward: rows (B V, h, w, C) dense channels-last, 16-byte aligned; points (r^3, 3) dense f32 in (d, h, w) grid order;
+ *   w2cs (B V, 4, 4), ixts (B V, 3, 3) dense f32, the intrinsics of an (img_h, img_w) image; view_embed: rows of (V, E) or NULL
+ *   with E = 0; cond (B g^3, V bs^3, C + E) dense, 16-byte aligned, g = n_group, bs = r / g.  keys (int64) and weights (f32), 4 B V
+ *   r^3 entries each or both NULL: the tap table the backward reads.  1 launch.
+ * sample_backward: grad_cond dense like cond; grad_rows like rows (written whole), grad_view_embed (V, E) dense; a NULL output is
+ *   not wanted.  workspace (only with grad_rows): gdr_volcond_sample_backward_bytes(a) bytes, 256-byte aligned.
+ *   gdr_serial_sort on the bits of B V h w + 1 launch, + 1 launch with grad_view_embed.
+ * Envelope of sample (GDR_ERR_UNSUPPORTED beyond it): C a multiple of 8 in 8..GDR_VOLCOND_MAX_CHANNELS, E a multiple of 8 or 0,
+ * h, w <= GDR_VOLCOND_MAX_SIDE, 4 B V r^3 <= GDR_VOLCOND_MAX_ENTRIES (what gdr_serial_sort takes), n_group divides r. */
+#define GDR_VOLCOND_SLAB_ROWS 32
+#define GDR_VOLCOND_MAX_CHANNELS 4096
+#define GDR_VOLCOND_MAX_SIDE 1024
+#define GDR_VOLCOND_MAX_ENTRIES (1 << 30)
+typedef struct {
+    int32_t B, V, h, w, C, E, r, n_group, img_h, img_w;
+} gdr_volcond_sample_args;
+int gdr_volcond_ray_sh(const void* rays, int32_t rays_dtype, int64_t n, int32_t silu, float* out, void* stream);
+int gdr_volcond_modln_forward(const void* x, int64_t x_stride, int64_t x_inner, int64_t x_outer_stride, int32_t x_dtype,
+                              const void* shift_scale, int64_t ss_stride, int32_t ss_dtype, const void* weight, int32_t weight_dtype, const void* bias, int32_t bias_dtype,
+                              int64_t R, int32_t C, float eps, void* out, int32_t out_dtype, void* stream);
+size_t gdr_volcond_modln_backward_bytes(int64_t R, int32_t C);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_volcond_modln_backward(const void* grad_out, int64_t grad_stride, int32_t grad_dtype, const void* x, int64_t x_stride,
+                               int64_t x_inner, int64_t x_outer_stride, int32_t x_dtype, const void* shift_scale, int64_t ss_stride, int32_t ss_dtype, const void* weight,
+                               int32_t weight_dtype, const void* bias, int32_t bias_dtype, int64_t R, int32_t C, float eps,
+                               void* workspace, size_t workspace_bytes, void* grad_x, void* grad_shift_scale, void* grad_weight,
+                               void* grad_bias, void* stream);
+int gdr_volcond_sample_forward(const gdr_volcond_sample_args* a, const void* rows, int32_t rows_dtype, const float* points,
+                               const float* w2cs, const float* ixts, const void* view_embed, int64_t ve_stride, int32_t ve_dtype,
+                               void* cond, int32_t cond_dtype, int64_t* keys, float* weights, void* stream);
+size_t gdr_volcond_sample_backward_bytes(const gdr_volcond_sample_args* a);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_volcond_sample_backward(const gdr_volcond_sample_args* a, const void* grad_cond, int32_t grad_dtype, const int64_t* keys,
+                                const float* weights, void* workspace, size_t workspace_bytes, void* grad_rows, int32_t rows_dtype,
+                                void* grad_view_embed, int32_t ve_dtype, void* stream);
+
 /* ---- host-boundary helper: *flag |= 1 if the n_bytes (a multiple of 4; a, b 16-byte aligned) at a and b differ in any
  * 32-bit word.  Used by the Python boundary to verify that two calls of one render group were handed the same activated
  * tensors (see generativedensification_amd/viewgroup.py); one read of both buffers, no host synchronisation. */
