@@ -22,10 +22,11 @@
 // same workgroup.  dp_ij - sum_w p_iw dp_iw is taken as (dp_ij - pivot) - mean(dp - pivot), pivot = dp of the first key that
 // has the largest s (csrc/viewattn.hip explains why); with one key p = 1 and ds = 0 exactly.
 //
-// Mapping of the norms: csrc/norm.hip's, a row per group of LC lanes (row_io.h row_shape, row_stats).  The backward gives a
-// workgroup GDR_GROUPATTN_NORM_ROWS consecutive patch rows, keeps the weight / bias sums of a group's rows in registers, adds
-// the groups through LDS pairwise (tree_sum) and leaves one partial pair per workgroup; the fold launch adds the partials
-// (16 lanes per channel, each a run of workgroups in ascending order, then those 16 pairwise).
+// Mapping of the norms: csrc/norm.hip's, a row per group of LC lanes (row_io.h row_shape, row_stats; ln_rows.h for the row
+// load, the backward's tail, the LDS sum and the fold).  The backward gives a workgroup GDR_GROUPATTN_NORM_ROWS consecutive
+// patch rows, keeps the weight / bias sums of a group's rows in registers, adds the groups through LDS pairwise (sum_groups<true>,
+// both vectors behind one barrier) and leaves one partial pair per workgroup; the fold launch (ln_fold_kernel<true>) adds the
+// partials (16 lanes per column, each a run of workgroups in ascending order, then those 16 pairwise).
 //
 // Bounds: every lane checks its item against the counts of its workgroup; the row map is a bijection of [0, B D H W) (the
 // host checks that D, H, W are multiples of bs); no index depends on a loaded value, so non-finite inputs give unspecified
@@ -33,6 +34,7 @@
 #include "gdr_common.h"
 #include "host_util.h"
 #include "row_io.h"
+#include "ln_rows.h"
 
 namespace gdr {
 namespace {
@@ -214,35 +216,19 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_bwd_kernel(const GaP p) {
 }
 
 // ---- the row-map LayerNorms --------------------------------------------------------------------------------------------------
-constexpr int RM_BLOCK = 256;
+constexpr int RM_BLOCK = LN_BLOCK;
 constexpr int RM_ROWS = GDR_GROUPATTN_NORM_ROWS;
-constexpr int RM_FOLD_LANES = 16;
-constexpr int RM_FOLD_CH = RM_BLOCK / RM_FOLD_LANES;
 constexpr int64_t RM_MAX_ROWS = INT64_C(0x7fffffff);
 
 // unpatch = 0: x and dx are the volume (read / written through the map), out, copy and both gradients are in patch order;
 // unpatch = 1: x and dx are in patch order, out and grad are the volume
 struct RmP {
     const void* x; const void* weight; const void* bias; const void* grad; const void* grad_copy; void* out; void* copy; void* dx;
-    void* dweight; void* dbias; float* part;
+    float* part;                      // (workgroups, 2, C): dweight, dbias of a workgroup's rows
     int64_t N;
-    int32_t D, H, W, bs, C, lc_shift, unpatch, x_dt, copy_dt, w_dt, b_dt, out_dt, grad_dt, gcopy_dt, nparts;
+    int32_t D, H, W, bs, C, lc_shift, unpatch, x_dt, copy_dt, w_dt, b_dt, out_dt, grad_dt, gcopy_dt;
     float eps;
 };
-
-// the sum of v[0], v[stride], ... (n <= 32 values), pairwise in a fixed order: a chain of 32 additions carries several times
-// the rounding of five levels
-__device__ __forceinline__ float tree_sum(const float* v, int stride, int n) {
-    float a[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) a[i] = i < n ? v[i * stride] : 0.f;
-#pragma unroll
-    for (int w = 16; w > 0; w >>= 1) {
-#pragma unroll
-        for (int i = 0; i < w; ++i) a[i] += a[i + w];
-    }
-    return a[0];
-}
 
 // the voxel row of patch row r
 __device__ __forceinline__ int64_t voxel_row(const RmP& p, int64_t r) {
@@ -268,27 +254,22 @@ __global__ __launch_bounds__(RM_BLOCK) void rowmap_norm_fwd_kernel(const RmP p) 
     const int64_t vox = voxel_row(p, row), src = p.unpatch ? row : vox, dst = p.unpatch ? vox : row;
     float x[K][8];
     bool on[K];
+    pieces_on<K>(l, lc, p.C, on);
+    load_row<K>(p.x, src * p.C, p.x_dt, on, l, lc, x);
+    if (p.copy) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int c0 = (l + k * lc) * 8;
-        on[k] = c0 < p.C;
-        if (on[k]) {
-            load8(p.x, src * p.C + c0, p.x_dt, x[k]);
-            if (p.copy) {
-                store8(p.copy, row * p.C + c0, p.copy_dt, x[k]);
+        for (int k = 0; k < K; ++k)
+            if (on[k]) {
+                store8(p.copy, row * p.C + piece_c0(l, lc, k), p.copy_dt, x[k]);
                 round8(x[k], p.x_dt, p.copy_dt);
             }
-        } else {
-#pragma unroll
-            for (int v = 0; v < 8; ++v) x[k][v] = 0.f;
-        }
     }
     float mean, rstd;
     row_stats<K>(x, on, lc, 1.0f / (float)p.C, p.eps, mean, rstd);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (!on[k]) continue;
-        const int c0 = (l + k * lc) * 8;
+        const int c0 = piece_c0(l, lc, k);
         float y[8], a[8];
 #pragma unroll
         for (int v = 0; v < 8; ++v) y[v] = (x[k][v] - mean) * rstd;
@@ -317,26 +298,23 @@ __global__ __launch_bounds__(RM_BLOCK) void rowmap_norm_bwd_kernel(const RmP p) 
     const float inv_c = 1.0f / (float)C;
     bool on[K];
     float sc[K][8], accw[K][8], accb[K][8];
+    pieces_on<K>(l, lc, C, on);
+    fill_row<K>(accw, 0.f);
+    fill_row<K>(accb, 0.f);
+    fill_row<K>(sc, 1.f);
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        on[k] = (l + k * lc) * 8 < C;
-#pragma unroll
-        for (int v = 0; v < 8; ++v) { accw[k][v] = 0.f; accb[k][v] = 0.f; sc[k][v] = 1.f; }
-        if (on[k] && p.weight) load8(p.weight, (l + k * lc) * 8, p.w_dt, sc[k]);
-    }
+    for (int k = 0; k < K; ++k)
+        if (on[k] && p.weight) load8(p.weight, piece_c0(l, lc, k), p.w_dt, sc[k]);
     for (int64_t r = a + grp; r < e; r += G) {     // at most RM_ROWS / G rows, the same rows in every lane of a group
         const int64_t vox = voxel_row(p, r), xr = p.unpatch ? r : vox, gr = p.unpatch ? vox : r;
         float x[K][8], g[K][8];
+        load_row<K>(p.x, xr * C, p.x_dt, on, l, lc, x);
+        if (p.grad) load_row<K>(p.grad, gr * C, p.grad_dt, on, l, lc, g);
+        else fill_row<K>(g, 0.f);
+        if (!p.unpatch) {
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int c0 = (l + k * lc) * 8;
-#pragma unroll
-            for (int v = 0; v < 8; ++v) { x[k][v] = 0.f; g[k][v] = 0.f; }
-            if (on[k]) {
-                load8(p.x, xr * C + c0, p.x_dt, x[k]);
-                if (!p.unpatch) round8(x[k], p.x_dt, p.copy_dt);
-                if (p.grad) load8(p.grad, gr * C + c0, p.grad_dt, g[k]);
-            }
+            for (int k = 0; k < K; ++k)
+                if (on[k]) round8(x[k], p.x_dt, p.copy_dt);
         }
         float mean, rstd;
         row_stats<K>(x, on, lc, inv_c, p.eps, mean, rstd);
@@ -355,59 +333,23 @@ __global__ __launch_bounds__(RM_BLOCK) void rowmap_norm_bwd_kernel(const RmP p) 
                     m2 += gx * sc[k][v];
                 }
             }
-        m1 = group_sum(m1, lc) * inv_c;
-        m2 = group_sum(m2, lc) * inv_c;
+        ln_dx<K>(g, x, on, m1, m2, lc, inv_c, rstd);
 #pragma unroll
         for (int k = 0; k < K; ++k)
             if (on[k]) {
-                const int c0 = (l + k * lc) * 8;
-                float d[8];
-#pragma unroll
-                for (int v = 0; v < 8; ++v) d[v] = rstd * (g[k][v] - m1 - x[k][v] * m2);
+                const int c0 = piece_c0(l, lc, k);
                 if (p.grad_copy) {
                     float gc[8];
                     load8(p.grad_copy, r * C + c0, p.gcopy_dt, gc);
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) d[v] += gc[v];
+                    for (int v = 0; v < 8; ++v) g[k][v] += gc[v];
                 }
-                store8(p.dx, xr * C + c0, p.x_dt, d);
+                store8(p.dx, xr * C + c0, p.x_dt, g[k]);
             }
     }
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        if (on[k]) {
-#pragma unroll
-            for (int v = 0; v < 8; ++v) {
-                sh[grp * 2 * C + (l + k * lc) * 8 + v] = accw[k][v];
-                sh[grp * 2 * C + C + (l + k * lc) * 8 + v] = accb[k][v];
-            }
-        }
-    __syncthreads();
-    float* dst = p.part + (int64_t)blockIdx.x * 2 * C;
-    for (int c = tid; c < 2 * C; c += RM_BLOCK) dst[c] = tree_sum(sh + c, 2 * C, G);
-}
-
-// dweight[c] / dbias[c]: the partials of the workgroups in ascending order.  One workgroup per 16 of the 2 C columns.
-__global__ __launch_bounds__(RM_BLOCK) void rowmap_norm_fold_kernel(const RmP p) {
-    __shared__ float sh[RM_FOLD_LANES][RM_FOLD_CH];
-    const int tid = threadIdx.x, ch = tid & (RM_FOLD_CH - 1), fl = tid / RM_FOLD_CH, C = p.C;
-    const int col = blockIdx.x * RM_FOLD_CH + ch;
-    float acc = 0.f;
-    if (col < 2 * C) {
-        const int T = p.nparts, per = (T + RM_FOLD_LANES - 1) / RM_FOLD_LANES;
-        const int t0 = fl * per, t1 = t0 + per < T ? t0 + per : T;
-#pragma unroll 4
-        for (int t = t0; t < t1; ++t) acc += p.part[(int64_t)t * 2 * C + col];
-    }
-    sh[fl][ch] = acc;
-    __syncthreads();
-    if (fl != 0 || col >= 2 * C) return;
-    acc = tree_sum(&sh[0][ch], RM_FOLD_CH, RM_FOLD_LANES);
-    if (col < C) {
-        if (p.dweight) store1(p.dweight, col, p.w_dt, acc);
-    } else if (p.dbias) {
-        store1(p.dbias, col - C, p.b_dt, acc);
-    }
+    put_sums<K>(sh + grp * 2 * C, accw, on, l, lc);        // one LDS pass for the two vectors
+    put_sums<K>(sh + grp * 2 * C + C, accb, on, l, lc);
+    sum_groups<true>(sh, 2 * C, G, p.part + (int64_t)blockIdx.x * 2 * C);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
@@ -463,8 +405,7 @@ int norm_forward(int unpatch, const void* x, int32_t x_dtype, int32_t copy_dtype
     const int64_t groups = RM_BLOCK >> p.lc_shift;
     const dim3 grid((uint32_t)((N + groups - 1) / groups));
     const hipStream_t st = (hipStream_t)stream;
-    if (K == 1) hipLaunchKernelGGL(rowmap_norm_fwd_kernel<1>, grid, dim3(RM_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(rowmap_norm_fwd_kernel<2>, grid, dim3(RM_BLOCK), 0, st, p);
+    LN_LAUNCH_K(rowmap_norm_fwd_kernel, K, grid, st, p);
     return launch_status("groupattn rowmap_norm_fwd_kernel");
 }
 
@@ -485,20 +426,15 @@ int norm_backward(int unpatch, const void* grad_out, int32_t grad_dtype, const v
         return unsupported("groupattn norm backward: every row buffer must start on 16 bytes and the workspace on 256");
     if (workspace_bytes < norm_workspace(N, C)) return workspace_too_small("groupattn norm backward: workspace smaller than gdr_groupattn_norm_backward_bytes");
     RmP p = {};
-    p.x = x; p.weight = weight; p.grad = grad_out; p.grad_copy = grad_copy; p.dx = grad_x; p.dweight = grad_weight; p.dbias = grad_bias;
-    p.part = (float*)workspace;
+    p.x = x; p.weight = weight; p.grad = grad_out; p.grad_copy = grad_copy; p.dx = grad_x; p.part = (float*)workspace;
     p.N = N; p.D = D; p.H = H; p.W = W; p.bs = bs; p.C = C; p.unpatch = unpatch;
     p.x_dt = x_dtype; p.copy_dt = copy_dtype; p.w_dt = weight_dtype; p.b_dt = bias_dtype; p.grad_dt = grad_dtype; p.gcopy_dt = grad_copy_dtype; p.eps = eps;
-    p.nparts = (int32_t)((N + RM_ROWS - 1) / RM_ROWS);
+    const int64_t nparts = (N + RM_ROWS - 1) / RM_ROWS;
     int K;
     row_shape(C, &p.lc_shift, &K);
     const hipStream_t st = (hipStream_t)stream;
-    if (p.nparts) {
-        if (K == 1) hipLaunchKernelGGL(rowmap_norm_bwd_kernel<1>, dim3((uint32_t)p.nparts), dim3(RM_BLOCK), 0, st, p);
-        else hipLaunchKernelGGL(rowmap_norm_bwd_kernel<2>, dim3((uint32_t)p.nparts), dim3(RM_BLOCK), 0, st, p);
-    }
-    if (grad_weight || grad_bias)
-        hipLaunchKernelGGL(rowmap_norm_fold_kernel, dim3((uint32_t)((2 * C + RM_FOLD_CH - 1) / RM_FOLD_CH)), dim3(RM_BLOCK), 0, st, p);
+    if (nparts) LN_LAUNCH_K(rowmap_norm_bwd_kernel, K, dim3((uint32_t)nparts), st, p);
+    if (grad_weight || grad_bias) launch_ln_fold<true>(p.part, nparts, C, grad_weight, weight_dtype, grad_bias, bias_dtype, st);
     return launch_status("groupattn rowmap_norm_bwd kernels");
 }
 

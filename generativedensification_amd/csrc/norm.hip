@@ -30,20 +30,23 @@
 //                 the result leaves in aligned 8-element pieces although the feat part starts at column 6F.  dfeat is summed
 //                 over the children in registers; dx over k by lanes 0..2 from an LDS row, k ascending.
 //
+// The pieces of a lane, the zero-filled row load, the backward's tail behind the element loop, the LDS sum of the groups and
+// the dispatch on the pieces per lane are ln_rows.h's, shared with groupattn.hip's and volcond.hip's norms; ada's fold is
+// segmented and stays here.
+//
 // Bounds: offset values are clamped to [0, N] where they are read; the searches stop after 16 steps; a piece consumes at
 // least one row; every row index is checked against N or P.  A malformed offset gives unspecified values and never an access
 // outside the buffers.
 #include "gdr_common.h"
 #include "host_util.h"
 #include "row_io.h"
+#include "ln_rows.h"
 
 namespace gdr {
 namespace {
 
-constexpr int NM_BLOCK = 256;
+constexpr int NM_BLOCK = LN_BLOCK;
 constexpr int NM_ROWS = GDR_NORM_ROWS;
-constexpr int NM_FOLD_LANES = 16;
-constexpr int NM_FOLD_CH = NM_BLOCK / NM_FOLD_LANES;
 constexpr int NM_TRIG = 6 * GDR_NORM_MAX_FREQS;      // trig columns of a pe row at most
 constexpr int NM_PE_EXTRA = NM_TRIG + NM_TRIG / 2;   // LDS floats of a group in the pe backward beside the gradient row
 
@@ -88,23 +91,15 @@ __global__ __launch_bounds__(NM_BLOCK) void ada_fwd_kernel(const AdaP p) {
     if (row >= p.N) return;                        // (whole groups leave: the butterflies stay inside a group)
     float x[K][8];
     bool on[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int c0 = (l + k * lc) * 8;
-        on[k] = c0 < p.C;
-        if (on[k]) load8(p.feat, row * p.feat_stride + c0, p.feat_dt, x[k]);
-        else {
-#pragma unroll
-            for (int v = 0; v < 8; ++v) x[k][v] = 0.f;
-        }
-    }
+    pieces_on<K>(l, lc, p.C, on);
+    load_row<K>(p.feat, row * p.feat_stride, p.feat_dt, on, l, lc, x);
     const int b = seg_of_row(p.offset, p.B, p.N, row);
     float mean, rstd;
     row_stats<K>(x, on, lc, 1.0f / (float)p.C, p.eps, mean, rstd);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (!on[k]) continue;
-        const int c0 = (l + k * lc) * 8;
+        const int c0 = piece_c0(l, lc, k);
         float y[8];
         if (b < p.B) {
             float sc[8];
@@ -127,8 +122,7 @@ __global__ __launch_bounds__(NM_BLOCK) void ada_bwd_kernel(const AdaP p) {
     const int C = p.C;
     const float inv_c = 1.0f / (float)C;
     bool on[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) on[k] = (l + k * lc) * 8 < C;
+    pieces_on<K>(l, lc, C, on);
     int64_t row = a;
     // (everything that steers the loop is the same in all threads of the workgroup)
     for (int it = 0; it < NM_ROWS && row < e; ++it) {
@@ -140,32 +134,19 @@ __global__ __launch_bounds__(NM_BLOCK) void ada_bwd_kernel(const AdaP p) {
             for (int64_t r = row + grp; r < e; r += G)
 #pragma unroll
                 for (int k = 0; k < K; ++k)
-                    if (on[k]) store8(p.dfeat, r * C + (l + k * lc) * 8, p.feat_dt, z);
+                    if (on[k]) store8(p.dfeat, r * C + piece_c0(l, lc, k), p.feat_dt, z);
             break;
         }
         const int64_t st = b ? clamp_end(p.offset, b - 1, N) : 0, en = clamp_end(p.offset, b, N);
         int64_t r1 = en < e ? en : e;
         if (r1 <= row) r1 = row + 1;               // (ends that are not monotone: one row on)
         float sc[K][8], acc[K][8];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-#pragma unroll
-            for (int v = 0; v < 8; ++v) { acc[k][v] = 0.f; sc[k][v] = 0.f; }
-            if (on[k]) load8(p.scale, (int64_t)b * p.scale_stride + (l + k * lc) * 8, p.scale_dt, sc[k]);
-        }
+        fill_row<K>(acc, 0.f);
+        load_row<K>(p.scale, (int64_t)b * p.scale_stride, p.scale_dt, on, l, lc, sc);
         for (int64_t r = row + grp; r < r1; r += G) {      // at most GDR_NORM_ROWS / G rows
             float x[K][8], g[K][8];
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const int c0 = (l + k * lc) * 8;
-                if (on[k]) {
-                    load8(p.feat, r * p.feat_stride + c0, p.feat_dt, x[k]);
-                    load8(p.grad, r * p.grad_stride + c0, p.out_dt, g[k]);
-                } else {
-#pragma unroll
-                    for (int v = 0; v < 8; ++v) { x[k][v] = 0.f; g[k][v] = 0.f; }
-                }
-            }
+            load_row<K>(p.feat, r * p.feat_stride, p.feat_dt, on, l, lc, x);
+            load_row<K>(p.grad, r * p.grad_stride, p.out_dt, on, l, lc, g);
             float mean, rstd;
             row_stats<K>(x, on, lc, inv_c, p.eps, mean, rstd);
             float m1 = 0.f, m2 = 0.f;
@@ -182,30 +163,13 @@ __global__ __launch_bounds__(NM_BLOCK) void ada_bwd_kernel(const AdaP p) {
                         m2 += gx * sc[k][v];
                     }
                 }
-            m1 = group_sum(m1, lc) * inv_c;
-            m2 = group_sum(m2, lc) * inv_c;
+            ln_dx<K>(g, x, on, m1, m2, lc, inv_c, rstd);
 #pragma unroll
             for (int k = 0; k < K; ++k)
-                if (on[k]) {
-                    float d[8];
-#pragma unroll
-                    for (int v = 0; v < 8; ++v) d[v] = rstd * (g[k][v] - m1 - x[k][v] * m2);
-                    store8(p.dfeat, r * C + (l + k * lc) * 8, p.feat_dt, d);
-                }
+                if (on[k]) store8(p.dfeat, r * C + piece_c0(l, lc, k), p.feat_dt, g[k]);
         }
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            if (on[k]) {
-#pragma unroll
-                for (int v = 0; v < 8; ++v) sh[grp * C + (l + k * lc) * 8 + v] = acc[k][v];
-            }
-        __syncthreads();
-        float* dst = (st >= a && en <= e) ? p.ws_seg + (int64_t)b * C : p.ws_part + (j * 2 + (st < a ? 0 : 1)) * C;
-        for (int c = tid; c < C; c += NM_BLOCK) {
-            float s = 0.f;
-            for (int g = 0; g < G; ++g) s += sh[g * C + c];            // group order: fixed
-            dst[c] = s;
-        }
+        put_sums<K>(sh + grp * C, acc, on, l, lc);
+        sum_groups<false>(sh, C, G, (st >= a && en <= e) ? p.ws_seg + (int64_t)b * C : p.ws_part + (j * 2 + (st < a ? 0 : 1)) * C);
         __syncthreads();
         row = r1;
     }
@@ -214,9 +178,9 @@ __global__ __launch_bounds__(NM_BLOCK) void ada_bwd_kernel(const AdaP p) {
 // dscale[b, c]: 0 for an empty segment, the finished sum of a segment that lies in one workgroup's rows, else the partials of
 // its workgroups in ascending order.  One workgroup per (segment, 16 channels).
 __global__ __launch_bounds__(NM_BLOCK) void ada_fold_kernel(const AdaP p, uint32_t ctiles) {
-    __shared__ float sh[NM_FOLD_LANES][NM_FOLD_CH];
-    const int tid = threadIdx.x, ch = tid & (NM_FOLD_CH - 1), fl = tid / NM_FOLD_CH;
-    const int b = blockIdx.x / ctiles, c = (int)(blockIdx.x % ctiles) * NM_FOLD_CH + ch, C = p.C;
+    __shared__ float sh[LN_FOLD_LANES][LN_FOLD_CH];
+    const int tid = threadIdx.x, ch = tid & (LN_FOLD_CH - 1), fl = tid / LN_FOLD_CH;
+    const int b = blockIdx.x / ctiles, c = (int)(blockIdx.x % ctiles) * LN_FOLD_CH + ch, C = p.C;
     const int64_t N = p.N;
     const int64_t st = b ? clamp_end(p.offset, b - 1, N) : 0, en = clamp_end(p.offset, b, N);
     float acc = 0.f;
@@ -225,7 +189,7 @@ __global__ __launch_bounds__(NM_BLOCK) void ada_fold_kernel(const AdaP p, uint32
         if (j0 == j1) {
             if (fl == 0) acc = p.ws_seg[(int64_t)b * C + c];
         } else {
-            const int64_t T = j1 - j0 + 1, per = (T + NM_FOLD_LANES - 1) / NM_FOLD_LANES;
+            const int64_t T = j1 - j0 + 1, per = (T + LN_FOLD_LANES - 1) / LN_FOLD_LANES;
             const int64_t t0 = fl * per, t1 = t0 + per < T ? t0 + per : T;
 #pragma unroll 4
             for (int64_t t = t0; t < t1; ++t) acc += p.ws_part[((j0 + t) * 2 + (t == 0 ? 1 : 0)) * C + c];
@@ -234,7 +198,7 @@ __global__ __launch_bounds__(NM_BLOCK) void ada_fold_kernel(const AdaP p, uint32
     sh[fl][ch] = acc;
     __syncthreads();
     if (fl != 0 || c >= C) return;
-    for (int i = 1; i < NM_FOLD_LANES; ++i) acc += sh[i][ch];
+    for (int i = 1; i < LN_FOLD_LANES; ++i) acc += sh[i][ch];
     store1(p.dscale, (int64_t)b * C + c, p.scale_dt, acc);
 }
 
@@ -493,8 +457,7 @@ int gdr_norm_ada_forward(const void* feat, int64_t feat_stride, int32_t feat_dty
     const int64_t groups = NM_BLOCK >> p.lc_shift;
     const dim3 grid((uint32_t)((N + groups - 1) / groups));
     const hipStream_t st = (hipStream_t)stream;
-    if (K == 1) hipLaunchKernelGGL(ada_fwd_kernel<1>, grid, dim3(NM_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(ada_fwd_kernel<2>, grid, dim3(NM_BLOCK), 0, st, p);
+    LN_LAUNCH_K(ada_fwd_kernel, K, grid, st, p);
     return launch_status("norm ada_fwd_kernel");
 }
 
@@ -526,11 +489,8 @@ int gdr_norm_ada_backward(const void* grad_out, int64_t grad_stride, int32_t gra
     row_shape(C, &p.lc_shift, &K);
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t chunks = (uint32_t)((N + NM_ROWS - 1) / NM_ROWS);
-    if (chunks) {
-        if (K == 1) hipLaunchKernelGGL(ada_bwd_kernel<1>, dim3(chunks), dim3(NM_BLOCK), 0, st, p);
-        else hipLaunchKernelGGL(ada_bwd_kernel<2>, dim3(chunks), dim3(NM_BLOCK), 0, st, p);
-    }
-    const uint32_t ctiles = (uint32_t)((C + NM_FOLD_CH - 1) / NM_FOLD_CH);
+    if (chunks) LN_LAUNCH_K(ada_bwd_kernel, K, dim3(chunks), st, p);
+    const uint32_t ctiles = (uint32_t)((C + LN_FOLD_CH - 1) / LN_FOLD_CH);
     hipLaunchKernelGGL(ada_fold_kernel, dim3((uint32_t)B * ctiles), dim3(NM_BLOCK), 0, st, p, ctiles);
     return launch_status("norm ada_bwd kernels");
 }

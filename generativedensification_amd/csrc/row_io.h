@@ -1,6 +1,7 @@
 // row_io.h — elements of a runtime storage type (GDR_NORM_F16 / BF16 / F32) <-> f32 on the device, the lane-group row sum and
-// the LayerNorm statistics of a row held by a lane group, as norm.hip, densify.hip, viewattn.hip and groupattn.hip use them
-// (internal; include after gdr_common.h).
+// the LayerNorm statistics of a row held by a lane group, as norm.hip, densify.hip, viewattn.hip, groupattn.hip and volcond.hip
+// use them; ln_rows.h builds the rest of what the three row LayerNorms share on top of this (internal; include after
+// gdr_common.h).
 #pragma once
 #include "half_bits.h"
 

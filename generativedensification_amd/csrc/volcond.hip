@@ -25,21 +25,23 @@
 // Everything is f32 arithmetic whatever the storage types.  No atomics: every output element has one writer and every sum a
 // fixed order, so two runs are bitwise equal.  No entry point allocates or synchronises.
 //
+// modln's row load, backward tail, LDS sum of the groups and fold (ln_fold_kernel<false>) are ln_rows.h's, shared with norm.hip
+// and groupattn.hip; make_taps and the 2^30 bound are proj_taps.h's, shared with pointfeat.hip.
+//
 // Bounds: every row index is checked against its count; texel coordinates are clamped into the map before an address is formed;
 // the searches of the backward stop after 32 steps and the entry indices they read come from the sort, which returns a
 // permutation of [0, entries).
 #include "gdr_common.h"
 #include "host_util.h"
 #include "row_io.h"
+#include "ln_rows.h"
+#include "proj_taps.h"
 
 namespace gdr {
 namespace {
 
-constexpr int VC_BLOCK = 256;
+constexpr int VC_BLOCK = LN_BLOCK;
 constexpr int VC_ROWS = GDR_VOLCOND_SLAB_ROWS;
-constexpr int VC_FOLD_LANES = 16;
-constexpr int VC_FOLD_CH = VC_BLOCK / VC_FOLD_LANES;
-constexpr float VC_MAX_POS = 1073741824.f;   // 2^30
 
 // ---- ray_sh ------------------------------------------------------------------------------------------------------------------
 // sqrt(1 / 4 pi); sqrt(3 / 4 pi); sqrt(15 / 4 pi), sqrt(5 / 16 pi), sqrt(15 / 16 pi); sqrt(35 / 32 pi), sqrt(105 / 4 pi),
@@ -92,9 +94,9 @@ __global__ __launch_bounds__(VC_BLOCK) void ray_sh_kernel(const void* __restrict
 // ---- modln -------------------------------------------------------------------------------------------------------------------
 struct ModP {
     const void *x, *ss, *weight, *bias, *grad;
-    void *out, *dx, *dss, *dweight, *dbias;
+    void *out, *dx, *dss;
     float* part;                      // (slabs, 2, C): dweight, dbias of a slab
-    int64_t R, x_stride, x_inner, x_outer, ss_stride, grad_stride, slabs;
+    int64_t R, x_stride, x_inner, x_outer, ss_stride, grad_stride;
     int32_t C, lc_shift, x_dt, ss_dt, w_dt, b_dt, out_dt;
     float eps;
 };
@@ -112,8 +114,8 @@ __device__ __forceinline__ void load_affine(const ModP& p, const bool (&on)[K], 
 #pragma unroll
         for (int v = 0; v < 8; ++v) { w[k][v] = 1.f; b[k][v] = 0.f; }
         if (on[k]) {
-            if (p.weight) load8(p.weight, (l + k * lc) * 8, p.w_dt, w[k]);
-            if (p.bias) load8(p.bias, (l + k * lc) * 8, p.b_dt, b[k]);
+            if (p.weight) load8(p.weight, piece_c0(l, lc, k), p.w_dt, w[k]);
+            if (p.bias) load8(p.bias, piece_c0(l, lc, k), p.b_dt, b[k]);
         }
     }
 }
@@ -125,21 +127,15 @@ __global__ __launch_bounds__(VC_BLOCK) void modln_fwd_kernel(const ModP p) {
     if (row >= p.R) return;                        // (whole groups leave: the butterflies stay inside a group)
     float x[K][8], w[K][8], b[K][8];
     bool on[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int c0 = (l + k * lc) * 8;
-        on[k] = c0 < p.C;
-#pragma unroll
-        for (int v = 0; v < 8; ++v) x[k][v] = 0.f;
-        if (on[k]) load8(p.x, x_offset(p, row) + c0, p.x_dt, x[k]);
-    }
+    pieces_on<K>(l, lc, p.C, on);
+    load_row<K>(p.x, x_offset(p, row), p.x_dt, on, l, lc, x);
     load_affine<K>(p, on, l, lc, w, b);
     float mean, rstd;
     row_stats<K>(x, on, lc, 1.0f / (float)p.C, p.eps, mean, rstd);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (!on[k]) continue;
-        const int c0 = (l + k * lc) * 8;
+        const int c0 = piece_c0(l, lc, k);
         float sh[8], sc[8], y[8];
         load8(p.ss, row * p.ss_stride + c0, p.ss_dt, sh);
         load8(p.ss, row * p.ss_stride + p.C + c0, p.ss_dt, sc);
@@ -159,33 +155,22 @@ __global__ __launch_bounds__(VC_BLOCK) void modln_bwd_kernel(const ModP p) {
     const int C = p.C;
     const float inv_c = 1.0f / (float)C;
     bool on[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) on[k] = (l + k * lc) * 8 < C;
+    pieces_on<K>(l, lc, C, on);
     float w[K][8], b[K][8], aw[K][8], ab[K][8];
     load_affine<K>(p, on, l, lc, w, b);
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-#pragma unroll
-        for (int v = 0; v < 8; ++v) { aw[k][v] = 0.f; ab[k][v] = 0.f; }
+    fill_row<K>(aw, 0.f);
+    fill_row<K>(ab, 0.f);
     for (int64_t r = a + grp; r < e; r += G) {
         float x[K][8], g[K][8];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int c0 = (l + k * lc) * 8;
-#pragma unroll
-            for (int v = 0; v < 8; ++v) { x[k][v] = 0.f; g[k][v] = 0.f; }
-            if (on[k]) {
-                load8(p.x, x_offset(p, r) + c0, p.x_dt, x[k]);
-                load8(p.grad, r * p.grad_stride + c0, p.out_dt, g[k]);
-            }
-        }
+        load_row<K>(p.x, x_offset(p, r), p.x_dt, on, l, lc, x);
+        load_row<K>(p.grad, r * p.grad_stride, p.out_dt, on, l, lc, g);
         float mean, rstd;
         row_stats<K>(x, on, lc, inv_c, p.eps, mean, rstd);
         float m1 = 0.f, m2 = 0.f;
 #pragma unroll
         for (int k = 0; k < K; ++k)
             if (on[k]) {
-                const int c0 = (l + k * lc) * 8;
+                const int c0 = piece_c0(l, lc, k);
                 float sc[8], ds[8];
                 load8(p.ss, r * p.ss_stride + C + c0, p.ss_dt, sc);
 #pragma unroll
@@ -208,55 +193,18 @@ __global__ __launch_bounds__(VC_BLOCK) void modln_bwd_kernel(const ModP p) {
                 }
             }
         if (p.dx) {                                // (the same in every thread)
-            m1 = group_sum(m1, lc) * inv_c;
-            m2 = group_sum(m2, lc) * inv_c;
+            ln_dx<K>(g, x, on, m1, m2, lc, inv_c, rstd);
 #pragma unroll
             for (int k = 0; k < K; ++k)
-                if (on[k]) {
-                    float d[8];
-#pragma unroll
-                    for (int v = 0; v < 8; ++v) d[v] = rstd * (g[k][v] - m1 - x[k][v] * m2);
-                    store8(p.dx, r * C + (l + k * lc) * 8, p.x_dt, d);
-                }
+                if (on[k]) store8(p.dx, r * C + piece_c0(l, lc, k), p.x_dt, g[k]);
         }
     }
     if (!p.part) return;                           // (the same in every thread)
-    for (int which = 0; which < 2; ++which) {
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            if (on[k]) {
-#pragma unroll
-                for (int v = 0; v < 8; ++v) lds[grp * C + (l + k * lc) * 8 + v] = which ? ab[k][v] : aw[k][v];
-            }
-        __syncthreads();
-        float* dst = p.part + (j * 2 + which) * C;
-        for (int c = tid; c < C; c += VC_BLOCK) {
-            float s = 0.f;
-            for (int g = 0; g < G; ++g) s += lds[g * C + c];           // group order: fixed
-            dst[c] = s;
-        }
-        __syncthreads();
-    }
-}
-
-// dweight[c], dbias[c]: the partials of the slabs in ascending order (16 contiguous ranges per channel, then those 16 in order).
-// One workgroup per (which, 16 channels).
-__global__ __launch_bounds__(VC_BLOCK) void modln_fold_kernel(const ModP p, uint32_t ctiles) {
-    __shared__ float sh[VC_FOLD_LANES][VC_FOLD_CH];
-    const int tid = threadIdx.x, ch = tid & (VC_FOLD_CH - 1), fl = tid / VC_FOLD_CH;
-    const int which = blockIdx.x / ctiles, c = (int)(blockIdx.x % ctiles) * VC_FOLD_CH + ch, C = p.C;
-    float acc = 0.f;
-    if (c < C) {
-        const int64_t T = p.slabs, per = (T + VC_FOLD_LANES - 1) / VC_FOLD_LANES;
-        const int64_t t0 = fl * per, t1 = t0 + per < T ? t0 + per : T;
-        for (int64_t t = t0; t < t1; ++t) acc += p.part[(t * 2 + which) * C + c];
-    }
-    sh[fl][ch] = acc;
+    put_sums<K>(lds + grp * C, aw, on, l, lc);
+    sum_groups<false>(lds, C, G, p.part + j * 2 * C);
     __syncthreads();
-    if (fl != 0 || c >= C) return;
-    for (int i = 1; i < VC_FOLD_LANES; ++i) acc += sh[i][ch];
-    if (which == 0) { if (p.dweight) store1(p.dweight, c, p.w_dt, acc); }
-    else if (p.dbias) store1(p.dbias, c, p.b_dt, acc);
+    put_sums<K>(lds + grp * C, ab, on, l, lc);
+    sum_groups<false>(lds, C, G, p.part + (j * 2 + 1) * C);
 }
 
 // ---- sample ------------------------------------------------------------------------------------------------------------------
@@ -278,10 +226,9 @@ __device__ __forceinline__ int64_t cond_row(const SampP& p, int b, int v, int64_
     return (blk * p.V + v) * ((int64_t)bs * bs * bs) + ((z % bs) * bs + y % bs) * bs + x % bs;
 }
 
-struct Taps { int xc[2], yc[2]; float wx[2], wy[2]; bool in[4]; };
-
-// the four neighbours of point n in view bv of the (h, w) map: texel coordinates clamped into the map, `in` says which really
-// lie inside, w their weights; index t = 2 * (y neighbour) + (x neighbour).  A degenerate pair has no neighbour inside.
+// the four neighbours of point n in view bv of the (h, w) map (proj_taps.h make_taps); a degenerate pair has none inside.  The
+// projection is proj_taps.h project's arithmetic written out: called from there the compiler fuses other products of the matrix
+// rows into FMAs, and the samples and saved weights move in the last bit.
 __device__ __forceinline__ Taps project_taps(const SampP& p, int bv, int64_t n) {
     const float* m = p.w2c + (int64_t)bv * 16;
     const float* k = p.ixt + (int64_t)bv * 9;
@@ -294,26 +241,14 @@ __device__ __forceinline__ Taps project_taps(const SampP& p, int bv, int64_t n) 
     const float h2 = k[6] * q0 + k[7] * q1 + k[8] * q2;
     bool ok = h2 != 0.f;
     float x = ok ? h0 / h2 : 0.f, y = ok ? h1 / h2 : 0.f;
-    ok = ok && fabsf(x) <= VC_MAX_POS && fabsf(y) <= VC_MAX_POS;       // (false for NaN and inf)
+    ok = ok && fabsf(x) <= PT_MAX_POS && fabsf(y) <= PT_MAX_POS;       // (false for NaN and inf)
     // the pixel of the (img_h, img_w) image -> normalised -> the position in the (h, w) map, as grid_sample un-normalises
     float u = (((x + 0.5f) / (float)p.img_w * 2.f - 1.f + 1.f) * (float)p.w - 1.f) / 2.f;
     float v = (((y + 0.5f) / (float)p.img_h * 2.f - 1.f + 1.f) * (float)p.h - 1.f) / 2.f;
-    ok = ok && fabsf(u) <= VC_MAX_POS && fabsf(v) <= VC_MAX_POS;
+    ok = ok && fabsf(u) <= PT_MAX_POS && fabsf(v) <= PT_MAX_POS;
     if (!ok) u = v = 0.f;
-    Taps t;
-    const float uf = floorf(u), vf = floorf(v);
-    const int x0 = (int)uf, y0 = (int)vf;          // |u|, |v| <= 2^30: exact, and x0 + 1 cannot overflow
-    t.wx[1] = u - uf; t.wx[0] = (uf + 1.f) - u;
-    t.wy[1] = v - vf; t.wy[0] = (vf + 1.f) - v;
-    bool xin[2], yin[2];
-    for (int i = 0; i < 2; ++i) {
-        xin[i] = ok && x0 + i >= 0 && x0 + i < p.w;
-        yin[i] = ok && y0 + i >= 0 && y0 + i < p.h;
-        t.xc[i] = min(max(x0 + i, 0), p.w - 1);
-        t.yc[i] = min(max(y0 + i, 0), p.h - 1);
-    }
-    for (int i = 0; i < 4; ++i) t.in[i] = yin[i >> 1] && xin[i & 1];
-    return t;
+    const Proj pr = {u, v, h2, ok};
+    return make_taps(pr, p.h, p.w);
 }
 
 // one group of LC lanes per (view, point) pair, lanes over channels
@@ -470,9 +405,8 @@ void fill_sample(SampP& p, const gdr_volcond_sample_args* a) {
     p.img_h = a->img_h; p.img_w = a->img_w;
     p.N = (int64_t)a->r * a->r * a->r;
     p.pairs = p.N * a->B * a->V; p.entries = p.pairs * 4; p.texels = (int64_t)a->B * a->V * a->h * a->w;
-    int sh = 3;
-    while (sh < 6 && (1 << sh) < a->C / 8) ++sh;
-    p.lc_shift = sh;
+    int K;                                         // (C may need more than two pieces: the kernels loop over them)
+    row_shape(a->C, &p.lc_shift, &K);
 }
 
 struct SampWs { size_t order, inverse, sort, sort_bytes, bytes; };
@@ -527,8 +461,7 @@ int gdr_volcond_modln_forward(const void* x, int64_t x_stride, int64_t x_inner, 
     const int64_t groups = VC_BLOCK >> p.lc_shift;
     const dim3 grid((uint32_t)((R + groups - 1) / groups));
     const hipStream_t st = (hipStream_t)stream;
-    if (K == 1) hipLaunchKernelGGL(modln_fwd_kernel<1>, grid, dim3(VC_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(modln_fwd_kernel<2>, grid, dim3(VC_BLOCK), 0, st, p);
+    LN_LAUNCH_K(modln_fwd_kernel, K, grid, st, p);
     return launch_status("volcond modln_fwd_kernel");
 }
 
@@ -560,20 +493,14 @@ int gdr_volcond_modln_backward(const void* grad_out, int64_t grad_stride, int32_
         return workspace_too_small("volcond_modln_backward: workspace smaller than gdr_volcond_modln_backward_bytes");
     ModP p = {};
     p.x = x; p.ss = shift_scale; p.weight = weight; p.bias = bias; p.grad = grad_out;
-    p.dx = grad_x; p.dss = grad_shift_scale; p.dweight = grad_weight; p.dbias = grad_bias; p.part = params ? (float*)workspace : nullptr;
-    p.R = R; p.x_stride = x_stride; p.x_inner = x_inner; p.x_outer = x_outer_stride; p.ss_stride = ss_stride; p.grad_stride = grad_stride; p.slabs = slabs;
+    p.dx = grad_x; p.dss = grad_shift_scale; p.part = params ? (float*)workspace : nullptr;
+    p.R = R; p.x_stride = x_stride; p.x_inner = x_inner; p.x_outer = x_outer_stride; p.ss_stride = ss_stride; p.grad_stride = grad_stride;
     p.C = C; p.x_dt = x_dtype; p.ss_dt = ss_dtype; p.w_dt = weight_dtype; p.b_dt = bias_dtype; p.out_dt = grad_dtype; p.eps = eps;
     int K;
     row_shape(C, &p.lc_shift, &K);
     const hipStream_t st = (hipStream_t)stream;
-    if (slabs) {
-        if (K == 1) hipLaunchKernelGGL(modln_bwd_kernel<1>, dim3((uint32_t)slabs), dim3(VC_BLOCK), 0, st, p);
-        else hipLaunchKernelGGL(modln_bwd_kernel<2>, dim3((uint32_t)slabs), dim3(VC_BLOCK), 0, st, p);
-    }
-    if (params) {
-        const uint32_t ctiles = (uint32_t)((C + VC_FOLD_CH - 1) / VC_FOLD_CH);
-        hipLaunchKernelGGL(modln_fold_kernel, dim3(2 * ctiles), dim3(VC_BLOCK), 0, st, p, ctiles);
-    }
+    if (slabs) LN_LAUNCH_K(modln_bwd_kernel, K, dim3((uint32_t)slabs), st, p);
+    if (params) launch_ln_fold<false>(p.part, slabs, C, grad_weight, weight_dtype, grad_bias, bias_dtype, st);
     return launch_status("volcond modln_bwd kernels");
 }
 
