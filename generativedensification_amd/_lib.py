@@ -377,6 +377,19 @@ _PROTOS = {
     "gdr_norm_pe_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                        C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "gdr_upscale_expand_forward": (C.c_int, [C.c_void_p, C.c_int32] * 2 + [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                             C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "gdr_upscale_expand_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p, C.c_int32] * 3 +
+                                    [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_float, C.c_int32, C.c_float] + [C.c_void_p] * 4),
+    "gdr_upscale_merge_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 2 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                            C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                            C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_upscale_merge_backward_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "gdr_upscale_merge_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                             C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                             C.c_void_p, C.c_size_t] + [C.c_void_p] * 4),
     "gdr_densify_select_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "gdr_densify_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),

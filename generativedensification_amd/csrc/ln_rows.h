@@ -1,4 +1,4 @@
-// ln_rows.h — what the three LayerNorms over a row held by a lane group share (norm.hip ada, groupattn.hip rowmap,
+// ln_rows.h — what the three LayerNorms over a row held by a lane group share (norm_rows.h ada for norm.hip and upscale.hip, groupattn.hip rowmap,
 // volcond.hip modln; internal): the pieces a lane holds, the zero-filled load of a row, the tail of the backward behind the
 // caller's element loop, the sum of the groups' register sums through LDS into a partial row (chain or pairwise), the fold
 // of (slabs, 2, C) partials into dweight / dbias with its launch, and the dispatch on the pieces per lane.

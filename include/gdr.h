@@ -875,6 +875,46 @@ int gdr_norm_pe_backward(const void* grad_out, int64_t grad_stride, int32_t grad
                          const void* feat, int64_t feat_stride, int32_t feat_dtype, const void* freq, int32_t freq_dtype, int64_t P,
                          int32_t S, int32_t C, int32_t F, float eps, void* grad_x, void* grad_feat, void* stream);
 
+/* ---- UpscaleModule's glue round its Linears (csrc/upscale.hip; backward-compatible additions to v17) -------------------------
+ * expand: from t = delta_x(in_f) to the child coordinates and the input of delta_f; merge: skip row + drop-path branch +
+ * AdaLayerNorm.  The arithmetic is restated in the header of csrc/upscale.hip; the row passes are norm.hip's (one source).
+ * The caller owns every buffer; all are device memory.  Every `*_dtype` is one of GDR_NORM_F16 / BF16 / F32 and the types of
+ * one call are independent; the arithmetic is f32.  Refusals happen before any launch; N = 0 returns GDR_OK without one; no
+ * entry point allocates or synchronises with the host.  No atomics: two runs are bitwise equal.  Envelope: norm's, with
+ * N (parents) and N * S below 2^31.  "Rows" as above.
+ *
+ * expand_forward: t (N, 3 S) dense; coord (N, 3) dense; rows of feat (N, C); freq: F values; half_grid = 0.5 * grid_size;
+ *   out_x (N S, 3) dense of out_x_dtype; h: rows of (N S, 6 F + C) through h_stride, padded with zeros to a multiple of 8.
+ *   1 launch.
+ * expand_backward: grad_h as pe_backward's grad_out, or NULL (zeros); grad_out_x (N S, 3) dense of out_x_dtype, or NULL (zeros);
+ *   grad_t (N, 3 S) of t_dtype, grad_coord (N, 3) of coord_dtype, grad_feat (N, C) dense of feat_dtype, 16-byte aligned; a NULL
+ *   output is not wanted and not stored.  1 launch.
+ * merge_forward: rows of skip (N, C), branch (N S, C), scale (B, C); keep: N S values or NULL (ones); offset: B int64, the
+ *   PARENTS' inclusive segment ends (clamped to [0, N] where they are read); out (N S, C) dense, 16-byte aligned; the rows of
+ *   parents at or behind offset[B - 1] are zeros.  1 launch.
+ * merge_backward: grad_out: rows of (N S, C).  grad_skip (N, C) of skip_dtype, grad_branch (N S, C) of branch_dtype, grad_scale
+ *   (B, C) of scale_dtype, dense, 16-byte aligned, written whole; a NULL output is not wanted and not stored.  workspace:
+ *   gdr_upscale_merge_backward_bytes(N, S, B, C) bytes, 256-byte aligned.  1 launch + the fold when grad_scale is wanted. */
+int gdr_upscale_expand_forward(const void* t, int32_t t_dtype, const void* coord, int32_t coord_dtype, const void* feat,
+                               int64_t feat_stride, int32_t feat_dtype, const void* freq, int32_t freq_dtype, int64_t N, int32_t S,
+                               int32_t C, int32_t F, float half_grid, int32_t absolute_pe, float eps, void* out_x, int32_t out_x_dtype,
+                               void* h, int64_t h_stride, int32_t h_dtype, void* stream);
+int gdr_upscale_expand_backward(const void* grad_h, int64_t grad_h_stride, int32_t grad_h_dtype, const void* grad_out_x,
+                                int32_t out_x_dtype, const void* t, int32_t t_dtype, const void* coord, int32_t coord_dtype,
+                                const void* feat, int64_t feat_stride, int32_t feat_dtype, const void* freq, int32_t freq_dtype,
+                                int64_t N, int32_t S, int32_t C, int32_t F, float half_grid, int32_t absolute_pe, float eps,
+                                void* grad_t, void* grad_coord, void* grad_feat, void* stream);
+int gdr_upscale_merge_forward(const void* skip, int64_t skip_stride, int32_t skip_dtype, const void* branch, int64_t branch_stride,
+                              int32_t branch_dtype, const void* keep, int32_t keep_dtype, const void* scale, int64_t scale_stride,
+                              int32_t scale_dtype, const int64_t* offset, int64_t N, int32_t S, int32_t B, int32_t C, float eps,
+                              void* out, int32_t out_dtype, void* stream);
+size_t gdr_upscale_merge_backward_bytes(int64_t N, int32_t S, int32_t B, int32_t C);   /* 0: the arguments are refused */
+int gdr_upscale_merge_backward(const void* grad_out, int64_t grad_stride, int32_t grad_dtype, const void* skip, int64_t skip_stride,
+                               int32_t skip_dtype, const void* branch, int64_t branch_stride, int32_t branch_dtype, const void* keep,
+                               int32_t keep_dtype, const void* scale, int64_t scale_stride, int32_t scale_dtype, const int64_t* offset,
+                               int64_t N, int32_t S, int32_t B, int32_t C, float eps, void* workspace, size_t workspace_bytes,
+                               void* grad_skip, void* grad_branch, void* grad_scale, void* stream);
+
 /* ---- densification masks of the point decoder (csrc/densify.hip; added in v17, backward-compatible) ------------------------
  * What the reference's MaskModule / MaskResModule do around their scores: per-segment top-k / top-p selection, the
  * straight-through gate and the split into selected and remaining rows.  The rules are restated in the header of
