@@ -163,6 +163,15 @@ class GdrAttnArgs(C.Structure):   # include/gdr.h gdr_attn_args
                 ("reserved2", C.c_float)]
 
 
+GDR_ATTN_F32 = 2     # the gather entry points only
+
+
+class GdrAttnGatherArgs(C.Structure):   # include/gdr.h gdr_attn_gather_args
+    _fields_ = [("N", C.c_int32), ("Tp", C.c_int32), ("batch", C.c_int32), ("H", C.c_int32), ("D", C.c_int32),
+                ("max_seqlen", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_float),
+                ("reserved2", C.c_float)]
+
+
 GDR_PF_MAX_VIEWS, GDR_PF_MAX_CHANNELS, GDR_PF_MAX_SIDE, GDR_PF_MAX_POINTS = 16, 4096, 16384, (1 << 31) - 1
 
 
@@ -337,6 +346,8 @@ _PROTOS = {
                                    C.c_void_p]),
     "gdr_attn_backward": (C.c_int, [C.POINTER(GdrAttnArgs), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gdr_attn_gather_forward": (C.c_int, [C.POINTER(GdrAttnGatherArgs)] + [C.c_void_p] * 8),
+    "gdr_attn_gather_backward": (C.c_int, [C.POINTER(GdrAttnGatherArgs)] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3),
     "gdr_serial_encode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                     C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "gdr_serial_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -22,8 +22,17 @@
 //   - the score s_ij is the same fma chain over d in all three places it is computed, so forward and backward agree on P.
 // DESIGN.md §13 has the instruction counts behind VALU-not-MFMA at D = 8, L = 48 and the LDS budget.
 //
+// The gather form (GA = true, gdr_attn_gather_*) is the same two kernels with the row order as a parameter: slot p of a
+// sequence reads row order[p] of a dense (N, 3, H, D) qkv of any of three dtypes (rounded to fp16 on load; BF = false), and
+// only the slot that is its row's own (inverse[order[p]] == p) stores, straight to that row.  The reference's padding puts a
+// row's second slot one sequence later at the same position; the backward workgroup of the own slot loads that next
+// sequence's Q, dO, lse and delta into the LDS it has, runs the key-row sweep over its real query rows too and adds into the
+// same f32 dK / dV registers before the one rounding.  No scratch, no atomics on memory; DESIGN.md §28.
+//
 // Memory safety does not depend on cu_seqlens being well formed (it lives on the device and is never read by the host):
-// boundaries are clamped to [0, total] and a sequence longer than RP is cut at RP rows.
+// boundaries are clamped to [0, total] and a sequence longer than RP is cut at RP rows.  Nor on order / inverse: a slot
+// index is below total = Tp by that clamp, an entry of order outside [0, N) makes its slot a row of zeros that stores nothing,
+// inverse is read only at such a checked row and only compared.
 #include <math.h>
 
 #include <type_traits>
@@ -45,8 +54,12 @@ struct AttnP {
     float* lse;              // (H, total) dense               (backward: read)
     const uint16_t* dout;    // backward: (total, H, D) through d0, d1, d2
     uint16_t* dqkv;          // backward: (total, 3, H, D) dense
+    const int64_t* order;    // gather form: (total) the row of the dense (N, 3, H, D) qkv that each slot holds
+    const int64_t* inverse;  // gather form: (N) the slot that is each row's own
+    float* out_full;         // gather form, forward: NULL or (N, H, D) f32, the result before any rounding
     int64_t q0, q1, q2, q3, d0, d1, d2;
     int32_t total, batch, H, fixed_len;
+    int32_t N, io_dtype, out_dtype;   // gather form: rows, the dtype of qkv / out / dout / dqkv, the dtype backward reads out in
     int32_t qkv_vec, dout_vec;   // rows are unit-stride and 16-byte aligned: 128-bit loads
     float scale;
 };
@@ -92,6 +105,58 @@ template <int D>
 __device__ __forceinline__ void zero_row(uint16_t* p) {
 #pragma unroll
     for (int c = 0; c < D / 8; ++c) reinterpret_cast<uint4*>(p)[c] = make_uint4(0, 0, 0, 0);
+}
+
+__device__ __forceinline__ float as_half(float x) { return up16<false>(down16<false>(x)); }   // what .half() keeps of x
+
+// gather form: one dense, 16-byte aligned row of D elements of the run-time dtype `dt` at element `at`, as f32: each rounded
+// to fp16 first (HALF), or as it is
+template <int D, bool HALF>
+__device__ __forceinline__ void load_row_rt(const void* base, int64_t at, int dt, float (&x)[D]) {
+    if (dt == GDR_ATTN_F32) {
+        const float4* s = reinterpret_cast<const float4*>(static_cast<const float*>(base) + at);
+#pragma unroll
+        for (int c = 0; c < D / 4; ++c) {
+            const float4 w = s[c];
+            x[4 * c] = w.x; x[4 * c + 1] = w.y; x[4 * c + 2] = w.z; x[4 * c + 3] = w.w;
+        }
+    } else if (dt == GDR_ATTN_BF16) {
+        const uint4* s = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(base) + at);
+#pragma unroll
+        for (int c = 0; c < D / 8; ++c) unpack8<true>(s[c], x + 8 * c);
+    } else {
+        const uint4* s = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(base) + at);
+#pragma unroll
+        for (int c = 0; c < D / 8; ++c) unpack8<false>(s[c], x + 8 * c);
+    }
+    if (HALF && dt != GDR_ATTN_F16) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) x[d] = as_half(x[d]);
+    }
+}
+
+template <int D>
+__device__ __forceinline__ void load_row_half(const void* base, int64_t at, int dt, float (&x)[D]) {
+    load_row_rt<D, true>(base, at, dt, x);
+}
+
+// gather form: x rounded to fp16 and then to `dt`, to one dense, 16-byte aligned row at element `at`
+template <int D>
+__device__ __forceinline__ void store_row_half(void* base, int64_t at, int dt, const float (&x)[D]) {
+    if (dt == GDR_ATTN_F16) {
+        store_row<D, false>(static_cast<uint16_t*>(base) + at, x);
+        return;
+    }
+    float y[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) y[d] = as_half(x[d]);
+    if (dt == GDR_ATTN_BF16) {
+        store_row<D, true>(static_cast<uint16_t*>(base) + at, y);
+    } else {
+        float4* s = reinterpret_cast<float4*>(static_cast<float*>(base) + at);
+#pragma unroll
+        for (int c = 0; c < D / 4; ++c) s[c] = make_float4(y[4 * c], y[4 * c + 1], y[4 * c + 2], y[4 * c + 3]);
+    }
 }
 
 // LDS rows: f32 while they are small, the 16-bit input words from D = 32 on (exact either way)
@@ -159,9 +224,46 @@ __device__ __forceinline__ void seq_range(const AttnP& p, int seq, int& start, i
     if (!tail && L > RP) L = RP;
 }
 
+// gather form: the row slot `tok` (< total) holds, or -1 for an entry outside the table's range
+__device__ __forceinline__ int64_t gather_row(const AttnP& p, int64_t tok) {
+    const int64_t v = p.order[tok];
+    return (v >= 0 && v < p.N) ? v : -1;
+}
+
+// Q (w = 0), K (1) or V (2) of head h: of token `row` through the strides, or (GA) of row `row` of the dense qkv, zeros for -1
+template <int D, bool BF, bool GA>
+__device__ __forceinline__ void load_qkv(const AttnP& p, int64_t row, int h, int w, float (&x)[D]) {
+    if constexpr (GA) {
+        if (row >= 0) {
+            load_row_half<D>(p.qkv, ((row * 3 + w) * p.H + h) * D, p.io_dtype, x);
+        } else {
+#pragma unroll
+            for (int d = 0; d < D; ++d) x[d] = 0.f;
+        }
+    } else {
+        load_row<D, BF>(p.qkv + row * p.q0 + w * p.q1 + (int64_t)h * p.q2, p.q3, p.qkv_vec, x);
+    }
+}
+
 __device__ __forceinline__ float exp_nat(float x) { return __expf(x); }   // v_exp_f32 of x * log2(e); exp(-inf) = 0
 
-template <int D, int RP, bool BF>
+// thread = key row j (k, v) against the n query rows in LDS (Q, dO, lse, delta): dv += sum_i P_ij dO_i and
+// dk += sum_i P_ij (dO_i . V_j - delta_i) Q_i, dk without the softmax scale
+template <int D, bool BF, typename S>
+__device__ __forceinline__ void key_sweep(const float (&k)[D], const float (&v)[D], const S* Q, const S* G, const float* lse,
+                                          const float* del, int n, float scale, float (&dk)[D], float (&dv)[D]) {
+    for (int i = 0; i < n; ++i) {
+        const S* Qi = Q + (size_t)i * D;
+        const S* Gi = G + (size_t)i * D;
+        const float s = lds_dot<D, BF>(k, Qi) * scale;
+        const float pi = exp_nat(s - lse[i]);
+        const float dp = lds_dot<D, BF>(v, Gi);
+        lds_axpy<D, BF>(pi, Gi, dv);
+        lds_axpy<D, BF>(pi * (dp - del[i]), Qi, dk);
+    }
+}
+
+template <int D, int RP, bool BF, bool GA>
 __global__ __launch_bounds__(AT_BLOCK) void attn_fwd_kernel(const AttnP p) {
     using S = typename Store<D>::type;
     constexpr int G = AT_BLOCK / RP;
@@ -173,28 +275,35 @@ __global__ __launch_bounds__(AT_BLOCK) void attn_fwd_kernel(const AttnP p) {
     const int h = hg * G + g;
     int start, L;
     seq_range<RP>(p, seq, start, L);
-    if (seq == p.batch) {   // rows no sequence owns: defined as zero
-        if (h < p.H)
-            for (int row = start + r; row < start + L; row += RP) {
-                zero_row<D>(p.out + ((int64_t)row * p.H + h) * D);
-                p.lse[(int64_t)h * p.total + row] = 0.f;
-            }
-        return;
+    if constexpr (!GA) {
+        if (seq == p.batch) {   // rows no sequence owns: defined as zero
+            if (h < p.H)
+                for (int row = start + r; row < start + L; row += RP) {
+                    zero_row<D>(p.out + ((int64_t)row * p.H + h) * D);
+                    p.lse[(int64_t)h * p.total + row] = 0.f;
+                }
+            return;
+        }
     }
     if (L == 0) return;
     const bool live = r < L && h < p.H;
     const int64_t tok = start + r;
+    int64_t row = tok;      // GA: the row this slot holds, and whether the slot is that row's own
+    bool own = true;
+    if constexpr (GA) {
+        row = live ? gather_row(p, tok) : -1;
+        own = row >= 0 && p.inverse[row] == tok;
+    }
     float q[D], t[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) q[d] = 0.f, t[d] = 0.f;
     S* myK = sK + (size_t)(g * RP + r) * D;
     S* myV = sV + (size_t)(g * RP + r) * D;
     if (live) {
-        const uint16_t* base = p.qkv + tok * p.q0 + (int64_t)h * p.q2;
-        load_row<D, BF>(base, p.q3, p.qkv_vec, q);
-        load_row<D, BF>(base + p.q1, p.q3, p.qkv_vec, t);
+        load_qkv<D, BF, GA>(p, row, h, 0, q);
+        load_qkv<D, BF, GA>(p, row, h, 1, t);
         lds_put<D, BF>(myK, t);
-        load_row<D, BF>(base + 2 * p.q1, p.q3, p.qkv_vec, t);
+        load_qkv<D, BF, GA>(p, row, h, 2, t);
         lds_put<D, BF>(myV, t);
     } else {   // rows past the sequence are read by the last key block: zeros, weighted by exp(-inf) = 0
         lds_put<D, BF>(myK, t);
@@ -202,6 +311,9 @@ __global__ __launch_bounds__(AT_BLOCK) void attn_fwd_kernel(const AttnP p) {
     }
     __syncthreads();
     if (!live) return;
+    if constexpr (GA) {
+        if (!own && !p.lse) return;   // a copy slot: nothing of it is stored
+    }
     const S* Kg = sK + (size_t)g * RP * D;
     const S* Vg = sV + (size_t)g * RP * D;
     float m = -INFINITY, l = 0.f, acc[D];
@@ -231,55 +343,86 @@ __global__ __launch_bounds__(AT_BLOCK) void attn_fwd_kernel(const AttnP p) {
     const float inv = 1.f / l;
 #pragma unroll
     for (int d = 0; d < D; ++d) acc[d] *= inv;
-    store_row<D, BF>(p.out + (tok * p.H + h) * D, acc);
-    p.lse[(int64_t)h * p.total + tok] = m + logf(l);
+    if constexpr (GA) {
+        if (own) {
+            store_row_half<D>(p.out, (row * p.H + h) * D, p.io_dtype, acc);
+            if (p.out_full) {
+                float4* f = reinterpret_cast<float4*>(p.out_full + (row * p.H + h) * D);
+#pragma unroll
+                for (int c = 0; c < D / 4; ++c) f[c] = make_float4(acc[4 * c], acc[4 * c + 1], acc[4 * c + 2], acc[4 * c + 3]);
+            }
+        }
+        if (p.lse) p.lse[(int64_t)h * p.total + tok] = m + logf(l);
+    } else {
+        store_row<D, BF>(p.out + (tok * p.H + h) * D, acc);
+        p.lse[(int64_t)h * p.total + tok] = m + logf(l);
+    }
 }
 
-template <int D, int RP, bool BF>
+template <int D, int RP, bool BF, bool GA>
 __global__ __launch_bounds__(AT_BLOCK) void attn_bwd_kernel(const AttnP p) {
     using S = typename Store<D>::type;
     constexpr int G = AT_BLOCK / RP;
     __shared__ __attribute__((aligned(16))) S sA[AT_BLOCK * D];   // sweep 1: K rows; sweep 2: Q rows
     __shared__ __attribute__((aligned(16))) S sB[AT_BLOCK * D];   // sweep 1: V rows; sweep 2: dO rows
     __shared__ float sLse[AT_BLOCK], sDel[AT_BLOCK];
+    __shared__ int sReal;                                          // GA: the real query rows of the next sequence
     const int HG = (p.H + G - 1) / G;
     const int seq = blockIdx.x / HG, hg = blockIdx.x % HG;
     const int g = threadIdx.x / RP, r = threadIdx.x % RP;
     const int h = hg * G + g;
     int start, L;
     seq_range<RP>(p, seq, start, L);
-    if (seq == p.batch) {
-        if (h < p.H)
-            for (int row = start + r; row < start + L; row += RP)
+    if constexpr (!GA) {
+        if (seq == p.batch) {
+            if (h < p.H)
+                for (int row = start + r; row < start + L; row += RP)
 #pragma unroll
-                for (int w = 0; w < 3; ++w) zero_row<D>(p.dqkv + (((int64_t)row * 3 + w) * p.H + h) * D);
-        return;
+                    for (int w = 0; w < 3; ++w) zero_row<D>(p.dqkv + (((int64_t)row * 3 + w) * p.H + h) * D);
+            return;
+        }
     }
     if (L == 0) return;
     const bool live = r < L && h < p.H;
     const int64_t tok = start + r;
+    int64_t row = tok;      // GA: the row this slot holds, and whether the slot is that row's own
+    bool own = true;
+    if constexpr (GA) {
+        row = live ? gather_row(p, tok) : -1;
+        own = row >= 0 && p.inverse[row] == tok;
+        if (threadIdx.x == 0) sReal = 0;
+    }
     S* myA = sA + (size_t)(g * RP + r) * D;
     S* myB = sB + (size_t)(g * RP + r) * D;
     const S* Ag = sA + (size_t)g * RP * D;
     const S* Bg = sB + (size_t)g * RP * D;
-    const uint16_t* base = p.qkv + tok * p.q0 + (int64_t)h * p.q2;
     float q[D], go[D], t[D];
     float lse_i = 0.f, delta = 0.f;
     if (live) {
-        load_row<D, BF>(base + p.q1, p.q3, p.qkv_vec, t);
+        load_qkv<D, BF, GA>(p, row, h, 1, t);
         lds_put<D, BF>(myA, t);
-        load_row<D, BF>(base + 2 * p.q1, p.q3, p.qkv_vec, t);
+        load_qkv<D, BF, GA>(p, row, h, 2, t);
         lds_put<D, BF>(myB, t);
-        load_row<D, BF>(base, p.q3, p.qkv_vec, q);
-        load_row<D, BF>(p.dout + tok * p.d0 + (int64_t)h * p.d1, p.d2, p.dout_vec, go);
-        load_row<D, BF>(p.out + (tok * p.H + h) * D, 1, 1, t);
+        load_qkv<D, BF, GA>(p, row, h, 0, q);
+        if constexpr (GA) {
+            if (own) {
+                load_row_half<D>(p.dout, (row * p.H + h) * D, p.io_dtype, go);
+                load_row_rt<D, false>(p.out, (row * p.H + h) * D, p.out_dtype, t);
+            } else {   // a copy slot's upstream gradient is zero, and delta with it
+#pragma unroll
+                for (int d = 0; d < D; ++d) go[d] = 0.f, t[d] = 0.f;
+            }
+        } else {
+            load_row<D, BF>(p.dout + tok * p.d0 + (int64_t)h * p.d1, p.d2, p.dout_vec, go);
+            load_row<D, BF>(p.out + (tok * p.H + h) * D, 1, 1, t);
+        }
 #pragma unroll
         for (int d = 0; d < D; ++d) delta = fmaf(go[d], t[d], delta);
         lse_i = p.lse[(int64_t)h * p.total + tok];
     }
     __syncthreads();
     // sweep 1, thread = query row i: dQ_i = scale sum_j P_ij (dO_i . V_j - delta_i) K_j
-    if (live) {
+    if (live && own) {
         float dq[D];
 #pragma unroll
         for (int d = 0; d < D; ++d) dq[d] = 0.f;
@@ -291,7 +434,8 @@ __global__ __launch_bounds__(AT_BLOCK) void attn_bwd_kernel(const AttnP p) {
         }
 #pragma unroll
         for (int d = 0; d < D; ++d) dq[d] *= p.scale;
-        store_row<D, BF>(p.dqkv + ((tok * 3 + 0) * p.H + h) * D, dq);
+        if constexpr (GA) store_row_half<D>(p.dqkv, ((row * 3 + 0) * p.H + h) * D, p.io_dtype, dq);
+        else store_row<D, BF>(p.dqkv + ((tok * 3 + 0) * p.H + h) * D, dq);
     }
     __syncthreads();
     if (live) {
@@ -301,28 +445,65 @@ __global__ __launch_bounds__(AT_BLOCK) void attn_bwd_kernel(const AttnP p) {
         sDel[g * RP + r] = delta;
     }
     __syncthreads();
-    if (!live) return;
+    if constexpr (!GA) {
+        if (!live) return;
+    }
     // sweep 2, thread = key row j: dV_j = sum_i P_ij dO_i, dK_j = scale sum_i P_ij (dO_i . V_j - delta_i) Q_i
     float (&k)[D] = q;     // the registers of q and dO now hold this thread's own key and value rows (L2 hits)
     float (&v)[D] = go;
-    load_row<D, BF>(base + p.q1, p.q3, p.qkv_vec, k);
-    load_row<D, BF>(base + 2 * p.q1, p.q3, p.qkv_vec, v);
     float dk[D], dv[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) dk[d] = 0.f, dv[d] = 0.f;
-    for (int i = 0; i < L; ++i) {
-        const S* Qi = Ag + (size_t)i * D;
-        const S* Gi = Bg + (size_t)i * D;
-        const float s = lds_dot<D, BF>(k, Qi) * p.scale;
-        const float pi = exp_nat(s - sLse[g * RP + i]);
-        const float dp = lds_dot<D, BF>(v, Gi);
-        lds_axpy<D, BF>(pi, Gi, dv);
-        lds_axpy<D, BF>(pi * (dp - sDel[g * RP + i]), Qi, dk);
+    const bool mine = live && own;   // (GA: a copy slot's dK and dV are formed by the workgroup of the row's own slot, below)
+    if (mine) {
+        load_qkv<D, BF, GA>(p, row, h, 1, k);
+        load_qkv<D, BF, GA>(p, row, h, 2, v);
+        key_sweep<D, BF>(k, v, Ag, Bg, sLse + g * RP, sDel + g * RP, L, p.scale, dk, dv);
     }
+    if constexpr (GA) {
+        // the reference's padding repeats the tail of a segment's last full sequence in the next one, at the same position:
+        // its real queries attend to those keys, and their dK / dV belong to this thread's row
+        int start2 = 0, L2 = 0;
+        if (seq + 1 < p.batch) seq_range<RP>(p, seq + 1, start2, L2);
+        const int64_t tok2 = (int64_t)start2 + r;
+        const bool copy = mine && r < L2 && tok2 != tok && gather_row(p, tok2) == row;
+        if (__syncthreads_or(copy)) {   // (the barrier: sweep 2 has read the LDS rows that are replaced now)
+            if (r < L2 && h < p.H) {
+                const int64_t row2 = gather_row(p, tok2);
+                const bool own2 = row2 >= 0 && p.inverse[row2] == tok2;
+                float d2 = 0.f;
+                load_qkv<D, BF, GA>(p, row2, h, 0, t);
+                lds_put<D, BF>(myA, t);
+                if (own2) load_row_half<D>(p.dout, (row2 * p.H + h) * D, p.io_dtype, t);
+                else
+#pragma unroll
+                    for (int d = 0; d < D; ++d) t[d] = 0.f;
+                lds_put<D, BF>(myB, t);
+                if (own2) {
+                    float o[D];
+                    load_row_rt<D, false>(p.out, (row2 * p.H + h) * D, p.out_dtype, o);
+#pragma unroll
+                    for (int d = 0; d < D; ++d) d2 = fmaf(t[d], o[d], d2);
+                    atomicMax(&sReal, r + 1);
+                }
+                sLse[g * RP + r] = p.lse[(int64_t)h * p.total + tok2];
+                sDel[g * RP + r] = d2;
+            }
+            __syncthreads();
+            // rows from sReal on are copies themselves (dO = 0, delta = 0: no contribution); so is any copy before it
+            if (copy) key_sweep<D, BF>(k, v, Ag, Bg, sLse + g * RP, sDel + g * RP, sReal, p.scale, dk, dv);
+        }
+    }
+    if (!mine) return;
 #pragma unroll
     for (int d = 0; d < D; ++d) dk[d] *= p.scale;
-    store_row<D, BF>(p.dqkv + ((tok * 3 + 1) * p.H + h) * D, dk);
-    store_row<D, BF>(p.dqkv + ((tok * 3 + 2) * p.H + h) * D, dv);
+    if constexpr (GA) {
+        store_row_half<D>(p.dqkv, ((row * 3 + 1) * p.H + h) * D, p.io_dtype, dk);
+        store_row_half<D>(p.dqkv, ((row * 3 + 2) * p.H + h) * D, p.io_dtype, dv);
+    } else {
+        store_row<D, BF>(p.dqkv + ((tok * 3 + 1) * p.H + h) * D, dk);
+        store_row<D, BF>(p.dqkv + ((tok * 3 + 2) * p.H + h) * D, dv);
+    }
 }
 
 // NULL if the arguments are inside the envelope
@@ -352,29 +533,30 @@ int row_vec(const void* ptr, const int64_t* strides, int n) {   // unit-stride, 
     return 1;
 }
 
-template <bool BWD, int D, int RP, bool BF>
+template <bool BWD, int D, int RP, bool BF, bool GA>
 void attn_launch1(const AttnP& p, int blocks, hipStream_t st) {
-    if (BWD) hipLaunchKernelGGL((attn_bwd_kernel<D, RP, BF>), dim3(blocks), dim3(AT_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((attn_fwd_kernel<D, RP, BF>), dim3(blocks), dim3(AT_BLOCK), 0, st, p);
+    if (BWD) hipLaunchKernelGGL((attn_bwd_kernel<D, RP, BF, GA>), dim3(blocks), dim3(AT_BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((attn_fwd_kernel<D, RP, BF, GA>), dim3(blocks), dim3(AT_BLOCK), 0, st, p);
 }
 
-template <bool BWD, int D, bool BF>
+template <bool BWD, int D, bool BF, bool GA>
 void attn_launch_rp(const AttnP& p, int rp, int batch, hipStream_t st) {
     const int G = AT_BLOCK / rp;
-    const int blocks = (batch + 1) * ((p.H + G - 1) / G);
-    if (rp == 64) attn_launch1<BWD, D, 64, BF>(p, blocks, st);
-    else if (rp == 128) attn_launch1<BWD, D, 128, BF>(p, blocks, st);
-    else attn_launch1<BWD, D, 256, BF>(p, blocks, st);
+    const int blocks = (batch + (GA ? 0 : 1)) * ((p.H + G - 1) / G);   // (the gather form has no rows behind the last sequence)
+    if (rp == 64) attn_launch1<BWD, D, 64, BF, GA>(p, blocks, st);
+    else if (rp == 128) attn_launch1<BWD, D, 128, BF, GA>(p, blocks, st);
+    else attn_launch1<BWD, D, 256, BF, GA>(p, blocks, st);
 }
 
+// dtype < 0: the gather form (fp16 arithmetic)
 template <bool BWD>
-int attn_launch(const gdr_attn_args* a, const AttnP& p, hipStream_t st) {
-    const int rp = a->max_seqlen <= 64 ? 64 : (a->max_seqlen <= 128 ? 128 : 256);
-    const bool bf = a->dtype == GDR_ATTN_BF16;
-#define GDR_ATTN_D(DD)                                                   \
-    if (bf) attn_launch_rp<BWD, DD, true>(p, rp, a->batch, st);          \
-    else attn_launch_rp<BWD, DD, false>(p, rp, a->batch, st)
-    switch (a->D) {
+int attn_launch(int D, int max_seqlen, int batch, int dtype, const AttnP& p, hipStream_t st) {
+    const int rp = max_seqlen <= 64 ? 64 : (max_seqlen <= 128 ? 128 : 256);
+#define GDR_ATTN_D(DD)                                                                       \
+    if (dtype < 0) attn_launch_rp<BWD, DD, false, true>(p, rp, batch, st);                   \
+    else if (dtype == GDR_ATTN_BF16) attn_launch_rp<BWD, DD, true, false>(p, rp, batch, st); \
+    else attn_launch_rp<BWD, DD, false, false>(p, rp, batch, st)
+    switch (D) {
         case 8: GDR_ATTN_D(8); break;
         case 16: GDR_ATTN_D(16); break;
         case 32: GDR_ATTN_D(32); break;
@@ -382,6 +564,29 @@ int attn_launch(const gdr_attn_args* a, const AttnP& p, hipStream_t st) {
     }
 #undef GDR_ATTN_D
     return launch_status(BWD ? "attn_bwd_kernel" : "attn_fwd_kernel");
+}
+
+// NULL if the arguments of the gather form are inside the envelope
+const char* attn_gather_check(const gdr_attn_gather_args* a) {
+    if (!a) return "attn_gather: NULL arguments";
+    if (a->dtype != GDR_ATTN_F16 && a->dtype != GDR_ATTN_BF16 && a->dtype != GDR_ATTN_F32)
+        return "attn_gather: dtype must be GDR_ATTN_F16, GDR_ATTN_BF16 or GDR_ATTN_F32";
+    if (a->D != 8 && a->D != 16 && a->D != 32 && a->D != 64) return "attn_gather: head dimension D must be 8, 16, 32 or 64";
+    if (a->H < 1) return "attn_gather: H must be >= 1";
+    if (a->N < 0 || a->Tp < 0 || a->batch < 0) return "attn_gather: negative N, Tp or batch";
+    if (a->max_seqlen < 1 || a->max_seqlen > GDR_ATTN_MAX_SEQLEN) return "attn_gather: max_seqlen must be in 1..256";
+    if (!(a->scale == a->scale) || a->scale - a->scale != 0.f) return "attn_gather: softmax scale is not finite";
+    if (((int64_t)a->batch + 1) * a->H > INT64_C(0x7fffffff)) return "attn_gather: batch * H exceeds the launch grid";
+    return nullptr;
+}
+
+AttnP attn_gather_params(const gdr_attn_gather_args* a, const void* qkv, const int64_t* order, const int64_t* inverse,
+                         const int32_t* cu_seqlens) {
+    AttnP p = {};
+    p.qkv = (const uint16_t*)qkv; p.cu = cu_seqlens; p.order = order; p.inverse = inverse;
+    p.total = a->Tp; p.batch = a->batch; p.H = a->H; p.N = a->N; p.io_dtype = a->dtype;
+    p.scale = a->scale;
+    return p;
 }
 
 }  // namespace
@@ -410,7 +615,7 @@ int gdr_attn_forward(const gdr_attn_args* a, const void* qkv, const int64_t* qkv
     p.total = a->total; p.batch = a->batch; p.H = a->H; p.fixed_len = a->fixed_len;
     p.qkv_vec = row_vec(qkv, qkv_strides, 4);
     p.scale = a->scale;
-    return attn_launch<false>(a, p, (hipStream_t)stream);
+    return attn_launch<false>(a->D, a->max_seqlen, a->batch, a->dtype, p, (hipStream_t)stream);
 }
 
 int gdr_attn_backward(const gdr_attn_args* a, const void* dout, const int64_t* dout_strides, const void* qkv,
@@ -432,7 +637,38 @@ int gdr_attn_backward(const gdr_attn_args* a, const void* dout, const int64_t* d
     p.qkv_vec = row_vec(qkv, qkv_strides, 4);
     p.dout_vec = row_vec(dout, dout_strides, 3);
     p.scale = a->scale;
-    return attn_launch<true>(a, p, (hipStream_t)stream);
+    return attn_launch<true>(a->D, a->max_seqlen, a->batch, a->dtype, p, (hipStream_t)stream);
+}
+
+int gdr_attn_gather_forward(const gdr_attn_gather_args* a, const void* qkv, const int64_t* order, const int64_t* inverse,
+                            const int32_t* cu_seqlens, void* out, float* out_full, float* lse, void* stream) {
+    if (const char* why = attn_gather_check(a)) return invalid_arg(why);
+    if (a->N == 0 || a->Tp == 0 || a->batch == 0) return GDR_OK;
+    if (!qkv || !order || !inverse || !cu_seqlens || !out) return invalid_arg("attn_gather_forward: NULL argument");
+    if (misaligned(qkv, 15) || misaligned(out, 15) || misaligned(out_full, 15) || misaligned(lse, 3) || misaligned(order, 7) ||
+        misaligned(inverse, 7) || misaligned(cu_seqlens, 3))
+        return invalid_arg("attn_gather_forward: unaligned buffer");
+    AttnP p = attn_gather_params(a, qkv, order, inverse, cu_seqlens);
+    p.out = (uint16_t*)out; p.out_full = out_full; p.lse = lse;
+    return attn_launch<false>(a->D, a->max_seqlen, a->batch, -1, p, (hipStream_t)stream);
+}
+
+int gdr_attn_gather_backward(const gdr_attn_gather_args* a, const void* dout, const void* qkv, const int64_t* order,
+                             const int64_t* inverse, const int32_t* cu_seqlens, const void* out, int32_t out_dtype,
+                             const float* lse, void* dqkv, void* stream) {
+    if (const char* why = attn_gather_check(a)) return invalid_arg(why);
+    if (out_dtype != GDR_ATTN_F16 && out_dtype != GDR_ATTN_BF16 && out_dtype != GDR_ATTN_F32)
+        return invalid_arg("attn_gather_backward: out_dtype must be GDR_ATTN_F16, GDR_ATTN_BF16 or GDR_ATTN_F32");
+    if (a->N == 0 || a->Tp == 0 || a->batch == 0) return GDR_OK;
+    if (!dout || !qkv || !order || !inverse || !cu_seqlens || !out || !lse || !dqkv)
+        return invalid_arg("attn_gather_backward: NULL argument");
+    if (misaligned(qkv, 15) || misaligned(out, 15) || misaligned(dout, 15) || misaligned(dqkv, 15) || misaligned(lse, 3) ||
+        misaligned(order, 7) || misaligned(inverse, 7) || misaligned(cu_seqlens, 3))
+        return invalid_arg("attn_gather_backward: unaligned buffer");
+    AttnP p = attn_gather_params(a, qkv, order, inverse, cu_seqlens);
+    p.out = (uint16_t*)out; p.out_dtype = out_dtype; p.lse = (float*)lse;
+    p.dout = (const uint16_t*)dout; p.dqkv = (uint16_t*)dqkv;
+    return attn_launch<true>(a->D, a->max_seqlen, a->batch, -1, p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -664,6 +664,39 @@ int gdr_attn_backward(const gdr_attn_args* a, const void* dout, const int64_t* d
                       const int64_t* qkv_strides, const int32_t* cu_seqlens, const void* out, const float* lse, void* dqkv,
                       void* stream);
 
+/* ---- the same attention read and written through the decoder's index tables (csrc/attn.hip; added in v17, backward-compatible)
+ * What SerializedAttention.forward of the reference runs around the call above, inside the same two kernels:
+ *   out = attn(qkv[order].half().reshape(-1, 3, H, D), cu_seqlens).reshape(-1, C).to(qkv.dtype)[inverse],   C = H D
+ * and that line's autograd.  qkv: (N, 3 C) dense from a 16-byte aligned base, `dtype` GDR_ATTN_F16 / BF16 / F32; every
+ * element is rounded to fp16 as .half() rounds it and the arithmetic is the fp16 path of gdr_attn_forward.  order: (Tp)
+ * int64, the point each padded slot holds; inverse: (N) int64, the slot that is each point's own; cu_seqlens: batch + 1
+ * int32 boundaries over the Tp slots.  out: (N, C) dense in qkv's dtype: slot p stores the fp16 result, converted, to row
+ * order[p] if inverse[order[p]] == p.  out_full: NULL, or (N, C) f32 that receives the same rows before any rounding.
+ * lse: NULL (nothing is kept for a backward; the copy slots then compute nothing), or (H, Tp) f32 per slot.
+ * backward: dout (N, C) dense in qkv's dtype (rounded to fp16 on load); out: (N, C) dense of `out_dtype`, read as it is for
+ * delta_i = sum_d dO_id O_id: the forward's out (with f16 qkv that is bitwise the backward of gdr_attn_backward on the gathered
+ * rows) or its out_full (a delta free of the result's rounding: for f32 and bf16 qkv); dqkv: (N, 3 C) dense in qkv's dtype.  The own slot of a row stores dQ, dK and dV, each row exactly once with plain
+ * stores: two calls are bitwise equal.  A row's copy one sequence later, at the same position (the reference's padding),
+ * has dQ = 0 and contributes to dK and dV: the workgroup of the own slot runs the key sweep over that next sequence too and
+ * adds in f32 before the one rounding (to fp16, then to qkv's dtype).
+ * Precondition for defined VALUES: order[inverse[i]] == i for every i, and every slot that is not its row's own sits one
+ * sequence behind it at the same position.  Memory safety needs no precondition: no table is read by the host, entries of
+ * order / inverse outside [0, N) / [0, Tp) are skipped and cu_seqlens is clamped to [0, Tp].
+ * Envelope: D in {8, 16, 32, 64}, H >= 1, 1 <= max_seqlen <= GDR_ATTN_MAX_SEQLEN, N and Tp >= 0; N == 0 or Tp == 0 is a
+ * no-op.  One launch each, no atomics, no scratch, no host synchronisation. */
+#define GDR_ATTN_F32 2     /* the gather entry points only */
+typedef struct gdr_attn_gather_args {
+    int32_t N, Tp, batch, H, D;
+    int32_t max_seqlen;              /* the patch size: no sequence is longer */
+    int32_t dtype, reserved;         /* GDR_ATTN_F16 / GDR_ATTN_BF16 / GDR_ATTN_F32: qkv, out, dout and dqkv */
+    float scale, reserved2;          /* softmax scale (the caller resolves the default D^-0.5) */
+} gdr_attn_gather_args;
+int gdr_attn_gather_forward(const gdr_attn_gather_args* a, const void* qkv, const int64_t* order, const int64_t* inverse,
+                            const int32_t* cu_seqlens, void* out, float* out_full, float* lse, void* stream);
+int gdr_attn_gather_backward(const gdr_attn_gather_args* a, const void* dout, const void* qkv, const int64_t* order,
+                             const int64_t* inverse, const int32_t* cu_seqlens, const void* out, int32_t out_dtype,
+                             const float* lse, void* dqkv, void* stream);
+
 /* ---- point serialization for the point decoder (csrc/serialize.hip; added in v17, backward-compatible) ------------------
  * What the reference's Point.serialization and SerializedAttention.get_padding_and_inverse compute with tensor ops: the
  * space-filling-curve code of every point's grid cell under up to GDR_SERIAL_MAX_ORDERS orders, the stable argsort of each
