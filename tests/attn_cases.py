@@ -5,6 +5,8 @@
   - every head has its own magnitude, so a head / token or head / channel transposition shows;
   - the upstream gradient differs per token and per channel;
   - lengths are mixed in one call (48, 48, 1, 7, 33, 0, 64, 256, 5), with a zero-length sequence in the middle;
+  - every head dimension runs under every row tile of the kernels (the `t64_`, `t128_` and `t256_` shapes), with sequences that
+    fill the tile, miss it by one row, are the smallest it can hold, and sit on and beside a multiple of the 8-key block;
   - the reference's layouts are there: sequences of 48, D = 8 with H = 20 and H = 32;
   - every D of the envelope appears with an H that is a multiple of nothing convenient (3, 5);
   - default and non-default softmax scales;
@@ -20,6 +22,11 @@ import math
 import torch
 
 MIXED = (48, 48, 1, 7, 33, 0, 64, 256, 5)
+# one tuple per row tile of the kernels (RP = 64, 128 or 256 rows per head, picked from max_seqlen): a sequence that fills the
+# tile, one that is one short of it, the smallest the tile can hold, lengths on and just past a multiple of the 8-key block
+T64 = (64, 63, 57, 56, 9, 8, 1, 0, 17, 48)
+T128 = (65, 127, 128, 0, 96, 1, 121)
+T256 = (129, 255, 256, 0, 200)
 
 # name -> (H, D, lengths, softmax_scale, rows beyond cu_seqlens[-1], layout)
 SHAPES = {
@@ -30,7 +37,22 @@ SHAPES = {
     "ref48_h20_d8": (20, 8, (48,) * 6, 8 ** -0.5, 0, "dense"),        # the call site passes its scale explicitly
     "ref48_h32_d8_sliced": (32, 8, (48,) * 5, None, 2, "sliced"),
     "short_h1_d8": (1, 8, (3, 1, 0, 2), None, 1, "dense"),
+    # every head dimension under every row tile; H is a multiple of neither 4 nor 2, the heads a workgroup holds at RP = 64 and
+    # 128; each tier has both scales, both layouts and both kinds of tail
+    "t64_h3_d8": (3, 8, T64, None, 0, "dense"),
+    "t64_h5_d16": (5, 16, T64, 0.2, 3, "sliced"),
+    "t64_h3_d32": (3, 32, T64, None, 5, "sliced"),
+    "t64_h5_d64": (5, 64, T64, 0.09, 0, "dense"),
+    "t128_h3_d8": (3, 8, T128, 0.3, 2, "sliced"),
+    "t128_h5_d16": (5, 16, T128, None, 0, "dense"),
+    "t128_h3_d32": (3, 32, T128, 0.15, 0, "sliced"),
+    "t128_h5_d64": (5, 64, T128, None, 4, "dense"),
+    "t256_h3_d8": (3, 8, T256, None, 3, "dense"),
+    "t256_h5_d16": (5, 16, T256, 0.2, 0, "sliced"),
+    "t256_h3_d32": (3, 32, T256, None, 0, "sliced"),
+    "t256_h5_d64": (5, 64, T256, 0.1, 6, "dense"),
 }
+TIERS = [name for name in SHAPES if name.startswith(("t64_", "t128_", "t256_"))]
 DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
 CASES = [(name, dt) for name in SHAPES for dt in DTYPES]
 MANT_BITS = {torch.float16: 10, torch.bfloat16: 7, torch.float32: 23}
@@ -38,6 +60,11 @@ MANT_BITS = {torch.float16: 10, torch.bfloat16: 7, torch.float32: 23}
 
 def max_seqlen(name):
     return max(SHAPES[name][2])
+
+
+def row_tile(max_seqlen):
+    """RP, the rows per head of a workgroup: the kernels' selection (csrc/attn.hip attn_launch)"""
+    return 64 if max_seqlen <= 64 else 128 if max_seqlen <= 128 else 256
 
 
 def cu_of(lengths):
@@ -143,3 +170,17 @@ def f32_lse(qkv, cu, scale):
         q, k = qkv[a:b, 0].float().transpose(0, 1), qkv[a:b, 1].float().transpose(0, 1)
         lse[:, a:b] = torch.logsumexp((q * scale) @ k.transpose(-2, -1), dim=-1)
     return lse
+
+
+def bits_differ(what, a, b):
+    """0 if a and b are equal bit for bit; else the number of elements that differ, after printing it with the largest
+    distance in units of the last place (the bit patterns read as sign-magnitude integers)"""
+    if torch.equal(a, b):
+        return 0
+    ints = []
+    for t in (a, b):
+        i = t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16).to(torch.int64)
+        ints.append(torch.where(i < 0, (-32768 if t.element_size() == 2 else -(1 << 31)) - i, i))
+    n = int((ints[0] != ints[1]).sum())
+    print(f"{what}: {n} of {a.numel()} elements differ, by at most {int((ints[0] - ints[1]).abs().max())} ulp")
+    return n

@@ -15,6 +15,9 @@ name -> (patch, offsets, H, D, softmax_scale):
   rp128_d16       128 rows per head, 50 copies, a non-default scale
   rp256_d64       256 rows per head, 16-bit LDS rows, 199 copies, then a segment with none
   exact_d32       no copies at all
+  rp64_.. rp256_  TILE_SHAPES: with the five above, every head dimension under every row tile of the kernels; each has a patch
+                  that fills its sequence with borrowed rows behind it (`full`: it fills the tile too, `min`: the smallest
+                  patch of its tile)
 """
 import functools
 
@@ -29,7 +32,39 @@ SHAPES = {
     "rp256_d64": (200, (201, 601), 2, 64, None),
     "exact_d32": (48, (96, 144), 5, 32, None),
 }
-COPIES = {"borrow47_h3_d8": 94, "cfg_stage0": 66, "rp128_d16": 50, "rp256_d64": 199, "exact_d32": 0}
+
+
+def _tile_offsets(patch):
+    """borrow47_h3_d8's recipe at any patch: segments of patch + 1 (patch - 1 copies behind a patch that fills its sequence),
+    2 patch (none), 30 (one short sequence), 0 (empty), 2 patch + 1 (patch - 1 copies behind two full patches)"""
+    ends, at = [], 0
+    for n in (patch + 1, 2 * patch, 30, 0, 2 * patch + 1):
+        at += n
+        ends.append(at)
+    return tuple(ends)
+
+
+# the other eight (D, row tile) pairs of the kernels: patches that fill the tile (64, 128, 256 rows per head), that are the
+# smallest the tile can hold (65, 129), and 57 = 7 blocks of 8 keys and one; H is odd, a multiple of neither 4 nor 2
+TILE_SHAPES = {
+    "rp64_full_d16": (64, _tile_offsets(64), 5, 16, None),
+    "rp64_d64": (57, _tile_offsets(57), 3, 64, 0.1),
+    "rp128_full_d8": (128, _tile_offsets(128), 3, 8, None),
+    "rp128_min_d32": (65, _tile_offsets(65), 5, 32, 0.15),
+    "rp128_full_d64": (128, _tile_offsets(128), 3, 64, None),
+    "rp256_full_d8": (256, _tile_offsets(256), 5, 8, 0.3),
+    "rp256_min_d16": (129, _tile_offsets(129), 3, 16, None),
+    "rp256_full_d32": (256, _tile_offsets(256), 3, 32, None),
+}
+SHAPES.update(TILE_SHAPES)
+TILES = list(TILE_SHAPES)
+COPIES = {"borrow47_h3_d8": 94, "cfg_stage0": 66, "rp128_d16": 50, "rp256_d64": 199, "exact_d32": 0,
+          "rp64_full_d16": 126, "rp64_d64": 112, "rp128_full_d8": 254, "rp128_min_d32": 128, "rp128_full_d64": 254,
+          "rp256_full_d8": 510, "rp256_min_d16": 256, "rp256_full_d32": 510}
+# a case whose draw leaves a CORRECT kernel less than a fifth of the accuracy bar (tests/test_serattn_cpu.py
+# test_a_correct_kernel_leaves_room_under_the_bar_on_every_tile_case) takes the next seed that does:
+# rp256_min_d16 used 0.91 of the bar in the f16 dQ with its own seed
+RESEED = {"rp256_min_d16": 1}
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 CASES = [(name, dt) for name in SHAPES for dt in DTYPES]
 
@@ -51,7 +86,7 @@ def _make(name, dt):
     patch, offsets, H, D, scale = SHAPES[name]
     dtype = DTYPES[dt]
     N, C = offsets[-1], H * D
-    seed = 2000 + sum(map(ord, name))
+    seed = 2000 + sum(map(ord, name)) + RESEED.get(name, 0)
     order, inverse, cu, _ = tables(offsets, patch, seed)
     assert order.numel() - N == COPIES[name] and bool((order[inverse] == torch.arange(N)).all())
     g = torch.Generator().manual_seed(seed + 1)

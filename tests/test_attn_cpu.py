@@ -1,8 +1,11 @@
 """CPU: the plain-torch attention restatement (tests/attn_ref.py) against autograd; mutants of it against the inputs of
-tests/attn_cases.py at the bars the GPU test applies; `padded_patches` on hand-worked examples; the `flash_attn` drop-in's
+tests/attn_cases.py at the bars the GPU test applies; the (D, row tile, dtype) kernels the case table selects, and the room a
+model of a correct kernel leaves under the bar on the tile cases; `padded_patches` on hand-worked examples; the `flash_attn` drop-in's
 names, signatures and argument errors; the gdr_attn_* exports and their refusals."""
 import ctypes as C
+import functools
 import inspect
+import itertools
 import os
 
 import pytest
@@ -14,9 +17,34 @@ import attn_ref as R
 
 def _truth(case, mut=None):
     """f64 (out, lse, dqkv) of the restatement on the half-rounded inputs of a case."""
-    qkv, dout = case["qkv"].double(), case["dout"].double()
-    out, lse = R.attention(qkv, case["cu"], case["scale"], mut=mut)
-    return out, lse, R.attention_backward(qkv, case["cu"], dout, case["scale"], mut=mut)
+    qkv, dout, rp = case["qkv"].double(), case["dout"].double(), AC.row_tile(case["max_seqlen"])
+    out, lse = R.attention(qkv, case["cu"], case["scale"], mut=mut, rp=rp)
+    return out, lse, R.attention_backward(qkv, case["cu"], dout, case["scale"], mut=mut, rp=rp)
+
+
+@functools.lru_cache(maxsize=None)
+def _judged(name, dt):
+    """a case with what every judgement of it needs, computed once and left unchanged: the case, its f64 truth, and per tensor
+    (out, dq, dk, dv) the pair (truth, bar), the bar of test_gpu_attn.py built from the torch half composition run on the CPU"""
+    dtype = AC.DTYPES[dt]
+    case = AC.make(name, dtype)
+    out, lse, dqkv = _truth(case)
+    pt_out, pt_dqkv = AC.torch_composition(case["qkv"], case["cu"], case["scale"], case["dout"])
+    pairs = [("out", out, pt_out)] + [("dqkv"[0] + "qkv"[i], dqkv[:, i], pt_dqkv[:, i]) for i in range(3)]
+    bars = {what: (t, AC.bar(float((pt.double() - t).abs().max()), dtype, t)) for what, t, pt in pairs}
+    return case, (out, lse, dqkv), bars
+
+
+def _beyond(name, dt, mut):
+    """the tensors of a case in which the mutant misses the truth by more than the bar"""
+    case, (out, lse, dqkv), bars = _judged(name, dt)
+    out_m, lse_m, dqkv_m = _truth(case, mut)
+    got = {"out": out_m, "dq": dqkv_m[:, 0], "dk": dqkv_m[:, 1], "dv": dqkv_m[:, 2]}
+    hits = [(name, dt, what) for what, (t, limit) in bars.items() if float((got[what] - t).abs().max()) > limit]
+    pt_lse = AC.f32_lse(case["qkv"], case["cu"], case["scale"])
+    if float((lse_m - lse).abs().max()) > AC.bar(float((pt_lse.double() - lse).abs().max()), torch.float32, lse):
+        hits.append((name, dt, "lse"))
+    return hits
 
 
 @pytest.mark.parametrize("name", ["mixed_h3_d8", "mixed_h5_d16_scaled", "short_h1_d8"])
@@ -50,24 +78,61 @@ def test_hot_head_overflows_f32_without_max_subtraction_and_has_one_key_rows():
 @pytest.mark.parametrize("mut", R.MUTANTS)
 def test_every_mutant_is_beyond_the_gpu_bars_on_some_case(mut):
     """The bar of test_gpu_attn.py, built here from the SAME torch half composition run on the CPU: a mutant must miss the
-    truth by more than 2 err_pt + ulp in at least one tensor of at least one case."""
+    truth by more than 2 err_pt + ulp in at least one tensor of at least one case.  A mistake of the row tile (R.TILE_MUTANTS)
+    must be that far off on one of the tile cases (AC.TIERS) of EVERY head dimension, since each D is a kernel of its own."""
     caught = []
     for name, dt in AC.CASES:
-        dtype = AC.DTYPES[dt]
-        case = AC.make(name, dtype)
-        out, lse, dqkv = _truth(case)
-        out_m, lse_m, dqkv_m = _truth(case, mut)
-        pt_out, pt_dqkv = AC.torch_composition(case["qkv"], case["cu"], case["scale"], case["dout"])
-        pairs = [("out", out_m, out, pt_out)] + [("dqkv"[0] + "qkv"[i], dqkv_m[:, i], dqkv[:, i], pt_dqkv[:, i]) for i in range(3)]
-        for what, m, t, pt in pairs:
-            if float((m - t).abs().max()) > AC.bar(float((pt.double() - t).abs().max()), dtype, t):
-                caught.append((name, dt, what))
-        pt_lse = AC.f32_lse(case["qkv"], case["cu"], case["scale"])
-        if float((lse_m - lse).abs().max()) > AC.bar(float((pt_lse.double() - lse).abs().max()), torch.float32, lse):
-            caught.append((name, dt, "lse"))
+        caught = _beyond(name, dt, mut)
         if caught:
             break
     assert caught, mut
+    if mut in R.TILE_MUTANTS:
+        tiles = (64, 128) if mut == "group_reads_first_head" else (64, 128, 256)     # (one head per workgroup at RP = 256)
+        by_kernel = {}
+        for name in AC.TIERS:
+            key = (AC.SHAPES[name][1], AC.row_tile(AC.max_seqlen(name)))
+            for dt in AC.DTYPES:
+                hits = _beyond(name, dt, mut)
+                if hits and key not in by_kernel:
+                    by_kernel[key] = hits
+        for key in sorted(by_kernel):
+            print(f"{mut}: D = {key[0]}, RP = {key[1]} caught by {by_kernel[key][0][:2]} in {[h[2] for h in by_kernel[key]]}")
+        assert {k for k in by_kernel if k[1] in tiles} == set(itertools.product((8, 16, 32, 64), tiles)), (mut, by_kernel)
+
+
+def test_the_case_table_reaches_every_head_dim_row_tile_and_dtype():
+    """a (D, RP, dtype) is a kernel of its own, forward and backward: the cases, each at its own max_seqlen, select all 24"""
+    reached = {(AC.SHAPES[name][1], AC.row_tile(AC.make(name, AC.DTYPES[dt])["max_seqlen"]), dt) for name, dt in AC.CASES}
+    assert reached == set(itertools.product((8, 16, 32, 64), (64, 128, 256), AC.DTYPES))
+    # ... and the tile cases alone do, with a full tile, one a row short of it and the smallest it holds (0 for the first tile)
+    tiers = {(AC.SHAPES[n][1], AC.row_tile(AC.max_seqlen(n))) for n in AC.TIERS}
+    assert tiers == set(itertools.product((8, 16, 32, 64), (64, 128, 256))) and len(AC.TIERS) == 12
+    for name in AC.TIERS:
+        H, _, lengths, *_ = AC.SHAPES[name]
+        rp = AC.row_tile(max(lengths))
+        assert {rp, rp - 1, rp // 2 + 1 if rp > 64 else 1, 0} <= set(lengths) and H % 2 and sum(lengths) <= 843
+    for tier in ("t64_", "t128_", "t256_"):      # both values of every other setting under every tile
+        rows = [AC.SHAPES[n] for n in AC.TIERS if n.startswith(tier)]
+        assert {r[3] is None for r in rows} == {True, False} and {r[5] for r in rows} == {"dense", "sliced"}
+        assert {r[4] == 0 for r in rows} == {True, False}
+
+
+@pytest.mark.parametrize("name", AC.TIERS)
+def test_a_correct_kernel_leaves_room_under_the_bar_on_every_tile_case(name):
+    """A condition on the INPUTS, not a tolerance on the kernel: R.kernel_model (f32 arithmetic, out rounded to the dtype, delta
+    from the rounded out, gradients rounded once) must stay within 0.8 of the bar in out, dQ, dK and dV, so that a correct
+    kernel that only sums in another order is not a coin flip against the bar on the GPU.  dQ is the tensor that crowds it:
+    delta comes from the rounded result.  A case over the cap gets another length order, never a wider cap."""
+    worst = 0.0
+    for dt in AC.DTYPES:
+        case, _, bars = _judged(name, dt)
+        out, dqkv = R.kernel_model(case["qkv"], case["cu"], case["dout"], case["scale"])
+        dqkv = dqkv.to(AC.DTYPES[dt])
+        got = {"out": out, "dq": dqkv[:, 0], "dk": dqkv[:, 1], "dv": dqkv[:, 2]}
+        shares = {what: float((got[what].double() - t).abs().max()) / limit for what, (t, limit) in bars.items()}
+        print(f"{name} {dt}: share of the bar " + " ".join(f"{w} {s:.2f}" for w, s in shares.items()))
+        worst = max(worst, *shares.values())
+    assert worst <= 0.8, (name, worst)
 
 
 def test_padded_patches_on_hand_worked_examples():

@@ -12,13 +12,17 @@ against the f64 restatement (tests/serattn_ref.py) computed from the same fp16-r
 all-torch composition on the same device (serattn_ref.torch_composition), ulp the spacing of the tensor's dtype at its largest
 magnitude.  Both errors are printed before the assertion.
 
+patch_size as a hint: the same tables under a patch_size of a higher row tile give the same bits, so the gather kernels of the
+three tiles check each other without a tolerance.
+
 Then: two runs are bitwise equal and nothing synchronises with the host, through the op and through the bound forward with
 the tables cached in the point; the bound forward under bf16 autocast at the bar of
 test_gpu_attn.test_the_call_as_the_reference_makes_it_under_bf16_autocast; vjp and no_grad; the fall-backs.
 
 Measured on an MI355X, worst err_hip / err_pt over the cases and out, dQ, dK, dV: 0.85 (f32 qkv), 1.02 (bf16), 2.58 (f16: dQ of
 rp256_d64, delta from the fp16 result as the bitwise equality demands); the closest any tensor came to its bar was 0.90 of it
-(that dQ), 0.42 for f32 and 0.26 for bf16."""
+(that dQ), 0.42 for f32 and 0.26 for bf16.  Over the eight tile cases (serattn_cases.TILE_SHAPES): 1.00,
+1.09 and 1.49 (f16 dQ of rp128_full_d8); closest 0.50, 0.28 and 0.54."""
 import functools
 import json
 import os
@@ -36,11 +40,12 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
-def _op(case, qkv=None, backward=True):
+def _op(case, qkv=None, backward=True, patch=None):
     from generativedensification_amd import serattn as S
 
     qkv = (case["qkv"] if qkv is None else qkv).detach().requires_grad_(backward)
-    out = S.serialized_attention(qkv, case["order"], case["inverse"], case["cu_t"], case["H"], case["patch"], case["scale"])
+    out = S.serialized_attention(qkv, case["order"], case["inverse"], case["cu_t"], case["H"], patch or case["patch"],
+                                 case["scale"])
     if backward:
         out.backward(case["dout"])
     return out.detach(), qkv.grad
@@ -125,6 +130,26 @@ def test_forward_and_gradients_against_f64(name, dt):
         results.append(_report(w, dqkv[:, sl].cpu(), t_dqkv[:, sl], pt_dqkv[:, sl].cpu(), dtype))
     for err, limit in results:
         assert err <= limit, (name, dt, results)
+
+
+@pytest.mark.parametrize("name,dt", [(name, dt) for name in SC.SHAPES if SC.SHAPES[name][0] <= 128 for dt in SC.DTYPES])
+def test_a_larger_patch_size_over_the_same_tables_gives_the_same_bits(name, dt):
+    """patch_size only picks the row tile (64, 128 or 256 rows per head): the same tables under a patch_size of every higher
+    tile give out and dqkv bit for bit, the borrowed rows' second contribution included.  The kernels of the three tiles are
+    compared with each other, with no tolerance."""
+    case = SC.make(name, dt, DEV)
+    out, dqkv = _op(case)
+    assert float(out.float().abs().max()) > 0 and float(dqkv.float().abs().max()) > 0
+    higher = [p for p in (100, 128, 200, 256) if AC.row_tile(p) > AC.row_tile(case["patch"])]
+    assert {AC.row_tile(p) for p in higher} == {rp for rp in (128, 256) if rp > AC.row_tile(case["patch"])}
+    differ = 0
+    for p in higher:
+        out_p, dqkv_p = _op(case, patch=p)
+        differ += AC.bits_differ(f"out at patch_size {p}", out_p, out)
+        for i, w in enumerate(("dq", "dk", "dv")):
+            sl = slice(i * case["C"], (i + 1) * case["C"])
+            differ += AC.bits_differ(f"{w} at patch_size {p}", dqkv_p[:, sl], dqkv[:, sl])
+    assert differ == 0, (name, dt)
 
 
 def _bound(mod, point):

@@ -6,6 +6,7 @@ that need no GPU."""
 import ast
 import ctypes
 import inspect
+import itertools
 import json
 import os
 import re
@@ -13,6 +14,8 @@ import re
 import pytest
 import torch
 
+import attn_cases as AC
+import attn_ref as R
 import serattn_cases as SC
 import serattn_ref as SR
 
@@ -84,7 +87,61 @@ def test_the_cases_are_what_their_names_say():
         copy = case["inverse"][case["order"]] != slots
         assert bool((case["order"][slots[copy] - patch] == case["order"][copy]).all())
         assert bool((case["inverse"][case["order"]][copy] == slots[copy] - patch).all())
-    assert len(SC.CASES) == 15
+    assert len(SC.CASES) == 39
+    # the tile cases, segment by segment: patch + 1 points, two patches, a short one, an empty one, two patches and a point
+    for name in SC.TILES:
+        patch, offsets, H, *_ = SC.SHAPES[name]
+        assert [b - a for a, b in zip((0,) + offsets, offsets)] == [patch + 1, 2 * patch, 30, 0, 2 * patch + 1]
+        assert SC.COPIES[name] == 2 * (patch - 1) and H % 2 and offsets[-1] <= 1312
+        cu = SC.make(name, "f16")["cu"]
+        assert [b - a for a, b in zip(cu[:-1], cu[1:])] == [patch] * 4 + [30] + [patch] * 3
+
+
+def test_the_case_table_reaches_every_head_dim_and_row_tile():
+    """a (D, RP) is a kernel of its own in the gather form, forward and backward: the cases select all twelve"""
+    reached = {(D, AC.row_tile(patch)) for patch, _, _, D, _ in SC.SHAPES.values()}
+    assert reached == set(itertools.product((8, 16, 32, 64), (64, 128, 256)))
+    # a patch that fills the tile under every tile, and the smallest patch of the two upper tiles
+    assert {64, 128, 256, 65, 129} <= {SC.SHAPES[name][0] for name in SC.TILES}
+
+
+def _kernel_model(case, dt):
+    """what a correct kernel of the gather form gives (attn_ref.kernel_model over the gathered rows): every element rounded to
+    fp16, f32 arithmetic, the result rounded to fp16 and then to qkv's dtype; delta from the fp16 result for f16 qkv and from
+    the f32 one for f32 and bf16 qkv; the two contributions of a point held twice summed in f32, then rounded to fp16 and to
+    qkv's dtype.  -> out (N, C), dqkv (N, 3 C) in qkv's dtype"""
+    dtype, H, C, Tp = SC.DTYPES[dt], case["H"], case["C"], case["order"].numel()
+    packed = case["qkv"][case["order"]].half().reshape(Tp, 3, H, C // H)
+    dslots = torch.zeros(Tp, C, dtype=torch.float16)
+    dslots[case["inverse"]] = case["dout"].half()
+    out, dpacked = R.kernel_model(packed, case["cu"], dslots.reshape(Tp, H, C // H), case["scale"],
+                                  delta_from_rounded=dtype == torch.float16)
+    dqkv = torch.zeros(case["N"], 3 * C).index_add_(0, case["order"], dpacked.reshape(Tp, 3 * C))
+    return out.reshape(Tp, C).to(dtype)[case["inverse"]], dqkv.half().to(dtype)
+
+
+@pytest.mark.parametrize("name", SC.TILES)
+def test_a_correct_kernel_leaves_room_under_the_bar_on_every_tile_case(name):
+    """A condition on the INPUTS, not a tolerance on the kernel (tests/test_attn_cpu.py has the packed form's): the model must
+    stay within 0.8 of the bar of test_gpu_serattn.py, built here from the all-torch composition run on the CPU, in out, dQ, dK
+    and dV and in all three dtypes."""
+    worst = 0.0
+    for dt, dtype in SC.DTYPES.items():
+        c = SC.make(name, dt)
+        q64, d64, C = c["qkv"].half().double(), c["dout"].half().double(), c["C"]
+        t_out = SR.forward(q64, c["order"], c["inverse"], c["cu"], c["H"], c["scale"])
+        t_dqkv = SR.backward(q64, c["order"], c["inverse"], c["cu"], c["H"], d64, c["scale"])
+        pt_out, pt_dqkv = SR.torch_composition(c["qkv"], c["order"], c["inverse"], c["cu"], c["H"], c["scale"], c["dout"])
+        out, dqkv = _kernel_model(c, dt)
+        assert out.dtype == dtype and dqkv.dtype == dtype
+        triples = [("out", out, t_out, pt_out)]
+        triples += [(w, dqkv[:, i * C:(i + 1) * C], t_dqkv[:, i * C:(i + 1) * C], pt_dqkv[:, i * C:(i + 1) * C])
+                    for i, w in enumerate(("dq", "dk", "dv"))]
+        shares = {w: float((got.double() - t).abs().max()) / AC.bar(float((pt.double() - t).abs().max()), dtype, t)
+                  for w, got, t, pt in triples}
+        print(f"{name} {dt}: share of the bar " + " ".join(f"{w} {s:.2f}" for w, s in shares.items()))
+        worst = max(worst, *shares.values())
+    assert worst <= 0.8, (name, worst)
 
 
 def self_and_point_reads():
