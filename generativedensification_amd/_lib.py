@@ -149,8 +149,11 @@ class GdrTsdfArgs(C.Structure):   # include/gdr.h gdr_tsdf_args
                 ("n_blocks", C.c_int32), ("voxel", C.c_float), ("trunc", C.c_float), ("lo", C.c_int32 * 3),
                 ("dims", C.c_int32 * 3)]
 
+# include/gdr.h GDR_F16 / GDR_BF16 / GDR_F32: the one table of storage type codes; each module's names below are these
+GDR_DTYPES = {"f16": 0, "bf16": 1, "f32": 2}
+
 GDR_ATTN_MAX_SEQLEN = 256
-GDR_ATTN_F16, GDR_ATTN_BF16 = 0, 1
+GDR_ATTN_F16, GDR_ATTN_BF16 = GDR_DTYPES["f16"], GDR_DTYPES["bf16"]
 GDR_ATTN_HEAD_DIMS = (8, 16, 32, 64)
 GDR_SERIAL_ORDERS = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
 GDR_SERIAL_MAX_ORDERS, GDR_SERIAL_MAX_DEPTH, GDR_SERIAL_MAX_POINTS = 8, 16, 1 << 30
@@ -163,7 +166,7 @@ class GdrAttnArgs(C.Structure):   # include/gdr.h gdr_attn_args
                 ("reserved2", C.c_float)]
 
 
-GDR_ATTN_F32 = 2     # the gather entry points only
+GDR_ATTN_F32 = GDR_DTYPES["f32"]     # the gather entry points only
 
 
 class GdrAttnGatherArgs(C.Structure):   # include/gdr.h gdr_attn_gather_args
@@ -180,15 +183,15 @@ class GdrPointfeatArgs(C.Structure):   # include/gdr.h gdr_pointfeat_args
                 ("reserved", C.c_int32)]
 
 
-GDR_SUBM_DTYPES = {"f16": 0, "bf16": 1, "f32": 2}
+GDR_SUBM_DTYPES = GDR_DTYPES
 GDR_SUBM_MAX_TAPS, GDR_SUBM_MAX_CHANNELS, GDR_SUBM_MAX_POINTS = 125, 512, 1 << 30
 
 
 GDR_SEG_ROWS, GDR_SEG_MAX_CHANNELS = 32, 65536
-GDR_SEG_DTYPES = {"f16": 0, "bf16": 1, "f32": 2, "i64": 3}
+GDR_SEG_DTYPES = {**GDR_DTYPES, "i64": 3}
 GDR_SEG_OPS = {"sum": 0, "mean": 1, "min": 2, "max": 3}
 
-GDR_NORM_DTYPES = {"f16": 0, "bf16": 1, "f32": 2}
+GDR_NORM_DTYPES = GDR_DTYPES
 GDR_NORM_ROWS, GDR_NORM_MAX_CHANNELS, GDR_NORM_MAX_SEGMENTS, GDR_NORM_MAX_FREQS, GDR_NORM_MAX_UPSCALE = 32, 1024, 1024, 16, 16
 
 

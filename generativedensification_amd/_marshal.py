@@ -42,9 +42,56 @@ def workspace(nbytes: int, dev):
     return (ws, *aligned_base(ws.data_ptr(), nbytes))
 
 
-# torch dtype -> the storage type code of the row kernels (GDR_NORM_F16 / BF16 / F32)
-NORM_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-               torch.float32: L.GDR_NORM_DTYPES["f32"]}
+# torch dtype -> storage type code (include/gdr.h GDR_F16 / GDR_BF16 / GDR_F32): the one map; a module that takes fewer
+# types, or more, derives its own from this
+DTYPES = {torch.float16: L.GDR_DTYPES["f16"], torch.bfloat16: L.GDR_DTYPES["bf16"], torch.float32: L.GDR_DTYPES["f32"]}
+
+
+def check_float(name, t, dims=None):
+    """`t` is a tensor of a dtype in DTYPES, with `dims` dimensions where that is given."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor, not {type(t).__name__}")
+    if t.dtype not in DTYPES:
+        raise TypeError(f"{name} must be float32, float16 or bfloat16, not {t.dtype}")
+    if dims is not None and t.dim() != dims:
+        raise ValueError(f"{name} must have {dims} dimension{'s' if dims > 1 else ''}, got {tuple(t.shape)}")
+
+
+def check_devices(named, no_cpu_text):
+    """Every (name, tensor) of `named` is on the GPU (else `no_cpu_text`, the module's own sentence) and on the first one's."""
+    for name, t in named:
+        if not t.is_cuda:
+            raise RuntimeError(no_cpu_text)
+    dev = named[0][1].device
+    for name, t in named:
+        if t.device != dev:
+            raise RuntimeError(f"{name} must live on {named[0][0]}'s device ({dev}), not {t.device}")
+
+
+def up8(c):
+    return (c + 7) // 8 * 8
+
+
+def rows2d(t, pad=False):
+    """t (rows, C) as the kernels read rows (host_util.h bad_rows): unit channel stride, a 16-byte aligned base, a row stride
+    that is a multiple of 8 and covers the row; itself where it is so already, one copy otherwise.  `pad`: the caller's C may
+    be no multiple of 8 (viewattn.py, H heads of 4), where only a copy with a padded stride has aligned rows."""
+    N, C = t.shape
+    if N and (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < C or t.data_ptr() % 16):
+        if not pad or C % 8 == 0:
+            return t.contiguous()
+        buf = torch.empty(N, up8(C), dtype=t.dtype, device=t.device)[:, :C]
+        buf.copy_(t)
+        return buf
+    return t
+
+
+def stride0(t, pad=False):
+    """The row stride to pass for rows2d's `t`.  torch reports any stride for a one-row tensor, so that one gets the least
+    the kernels accept: max(C, 8), or C rounded up to 8 for a caller with `pad`."""
+    if t.shape[0] > 1:
+        return t.stride(0)
+    return up8(t.shape[1]) if pad else max(t.shape[1], 8)
 
 
 def queried_workspace(query, name, dev, *args):
@@ -62,8 +109,8 @@ def dense(t):
 
 
 def dense_aligned(rows):
-    """`rows` dense from a 16-byte aligned base: itself where it is so already, one copy otherwise"""
-    if rows.numel() and (not rows.is_contiguous() or rows.data_ptr() % 16):
+    """`rows` (or None) dense from a 16-byte aligned base: itself where it is so already, one copy otherwise"""
+    if rows is not None and rows.numel() and (not rows.is_contiguous() or rows.data_ptr() % 16):
         rows = rows.contiguous()
         if rows.data_ptr() % 16:
             rows = rows.clone()

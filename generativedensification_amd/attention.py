@@ -22,7 +22,7 @@ __all__ = ["attn_varlen_qkvpacked", "attn_qkvpacked", "MAX_SEQLEN", "HEAD_DIMS"]
 
 MAX_SEQLEN = L.GDR_ATTN_MAX_SEQLEN
 HEAD_DIMS = L.GDR_ATTN_HEAD_DIMS
-_DTYPES = {torch.float16: L.GDR_ATTN_F16, torch.bfloat16: L.GDR_ATTN_BF16}
+_DTYPES = {d: M.DTYPES[d] for d in (torch.float16, torch.bfloat16)}     # the dense kernels take no float32
 
 
 class _AttnFunction(torch.autograd.Function):

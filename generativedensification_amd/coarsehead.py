@@ -55,7 +55,7 @@ SH_DIMS = (3, 12, 27, 48)
 # "torch" (the reference's lines, on purpose: the A/B of scripts/bench_coarsehead.py)
 HEAD_BACKEND = "hip"
 
-_DTYPES = M.NORM_DTYPES
+_DTYPES = M.DTYPES
 _dense = M.dense
 _NO_CPU = "the HIP coarse head runs on ROCm/HIP tensors only (no CPU fallback)"
 

@@ -41,7 +41,7 @@ MAX_CHANNELS = L.GDR_CONV3D_MAX_CHANNELS
 MAX_ROWS = (1 << 31) - 1
 BRICK = L.GDR_CONV3D_BRICK          # voxels (D, H, W) of one workgroup of the product kernel
 
-_DTYPES = M.NORM_DTYPES
+_DTYPES = M.DTYPES
 _NO_CPU = "the HIP convolution runs on ROCm/HIP tensors only (no CPU fallback)"
 
 

@@ -35,11 +35,9 @@
 // inverse is read only at such a checked row and only compared.
 #include <math.h>
 
-#include <type_traits>
-
 #include "gdr_common.h"
-#include "half_bits.h"
 #include "host_util.h"
+#include "row_io.h"
 
 namespace gdr {
 namespace {
@@ -64,23 +62,8 @@ struct AttnP {
     float scale;
 };
 
-template <bool BF>
-__device__ __forceinline__ void unpack8(const uint4 w, float* x) {
-    const uint32_t u[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        x[2 * e] = up16<BF>((uint16_t)(u[e] & 0xffffu));
-        x[2 * e + 1] = up16<BF>((uint16_t)(u[e] >> 16));
-    }
-}
-
-template <bool BF>
-__device__ __forceinline__ uint4 pack8(const float* x) {
-    uint32_t u[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) u[e] = (uint32_t)down16<BF>(x[2 * e]) | ((uint32_t)down16<BF>(x[2 * e + 1]) << 16);
-    return make_uint4(u[0], u[1], u[2], u[3]);
-}
+using gdr::load_row;    // row_io.h's rows of a run-time dtype, beside the <D, BF> rows of the dense kernels below
+using gdr::store_row;
 
 // one row of D 16-bit words from global memory, as f32
 template <int D, bool BF>
@@ -109,54 +92,28 @@ __device__ __forceinline__ void zero_row(uint16_t* p) {
 
 __device__ __forceinline__ float as_half(float x) { return up16<false>(down16<false>(x)); }   // what .half() keeps of x
 
-// gather form: one dense, 16-byte aligned row of D elements of the run-time dtype `dt` at element `at`, as f32: each rounded
-// to fp16 first (HALF), or as it is
-template <int D, bool HALF>
-__device__ __forceinline__ void load_row_rt(const void* base, int64_t at, int dt, float (&x)[D]) {
-    if (dt == GDR_ATTN_F32) {
-        const float4* s = reinterpret_cast<const float4*>(static_cast<const float*>(base) + at);
-#pragma unroll
-        for (int c = 0; c < D / 4; ++c) {
-            const float4 w = s[c];
-            x[4 * c] = w.x; x[4 * c + 1] = w.y; x[4 * c + 2] = w.z; x[4 * c + 3] = w.w;
-        }
-    } else if (dt == GDR_ATTN_BF16) {
-        const uint4* s = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(base) + at);
-#pragma unroll
-        for (int c = 0; c < D / 8; ++c) unpack8<true>(s[c], x + 8 * c);
-    } else {
-        const uint4* s = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(base) + at);
-#pragma unroll
-        for (int c = 0; c < D / 8; ++c) unpack8<false>(s[c], x + 8 * c);
-    }
-    if (HALF && dt != GDR_ATTN_F16) {
+// gather form: one dense, 16-byte aligned row of D elements of the run-time dtype `dt` at element `at`, as f32, each rounded
+// to fp16 first
+template <int D>
+__device__ __forceinline__ void load_row_half(const void* base, int64_t at, int dt, float (&x)[D]) {
+    load_row<D>(base, at, dt, x);
+    if (dt != GDR_ATTN_F16) {
 #pragma unroll
         for (int d = 0; d < D; ++d) x[d] = as_half(x[d]);
     }
 }
 
-template <int D>
-__device__ __forceinline__ void load_row_half(const void* base, int64_t at, int dt, float (&x)[D]) {
-    load_row_rt<D, true>(base, at, dt, x);
-}
-
 // gather form: x rounded to fp16 and then to `dt`, to one dense, 16-byte aligned row at element `at`
 template <int D>
 __device__ __forceinline__ void store_row_half(void* base, int64_t at, int dt, const float (&x)[D]) {
-    if (dt == GDR_ATTN_F16) {
+    if (dt == GDR_ATTN_F16) {      // (the dense kernels' own store: the composition over them is matched bit for bit)
         store_row<D, false>(static_cast<uint16_t*>(base) + at, x);
         return;
     }
     float y[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) y[d] = as_half(x[d]);
-    if (dt == GDR_ATTN_BF16) {
-        store_row<D, true>(static_cast<uint16_t*>(base) + at, y);
-    } else {
-        float4* s = reinterpret_cast<float4*>(static_cast<float*>(base) + at);
-#pragma unroll
-        for (int c = 0; c < D / 4; ++c) s[c] = make_float4(y[4 * c], y[4 * c + 1], y[4 * c + 2], y[4 * c + 3]);
-    }
+    store_row<D>(base, at, dt, y);
 }
 
 // LDS rows: f32 while they are small, the 16-bit input words from D = 32 on (exact either way)
@@ -407,7 +364,7 @@ __global__ __launch_bounds__(AT_BLOCK) void attn_bwd_kernel(const AttnP p) {
         if constexpr (GA) {
             if (own) {
                 load_row_half<D>(p.dout, (row * p.H + h) * D, p.io_dtype, go);
-                load_row_rt<D, false>(p.out, (row * p.H + h) * D, p.out_dtype, t);
+                load_row<D>(p.out, (row * p.H + h) * D, p.out_dtype, t);
             } else {   // a copy slot's upstream gradient is zero, and delta with it
 #pragma unroll
                 for (int d = 0; d < D; ++d) go[d] = 0.f, t[d] = 0.f;
@@ -481,7 +438,7 @@ __global__ __launch_bounds__(AT_BLOCK) void attn_bwd_kernel(const AttnP p) {
                 lds_put<D, BF>(myB, t);
                 if (own2) {
                     float o[D];
-                    load_row_rt<D, false>(p.out, (row2 * p.H + h) * D, p.out_dtype, o);
+                    load_row<D>(p.out, (row2 * p.H + h) * D, p.out_dtype, o);
 #pragma unroll
                     for (int d = 0; d < D; ++d) d2 = fmaf(t[d], o[d], d2);
                     atomicMax(&sReal, r + 1);

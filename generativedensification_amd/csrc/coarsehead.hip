@@ -34,8 +34,8 @@
 // tile bookkeeping, the fold, the backward's LDS carve) is head_rows.h.
 // Tile sizes, the step and where the weights sit are unmeasured choices.
 #include "gdr_common.h"
-#include "half_bits.h"
 #include "host_util.h"
+#include "row_io.h"
 #include "mfma_rows.h"
 #include "head_rows.h"
 
@@ -96,21 +96,21 @@ __global__ __launch_bounds__(HEAD_BLOCK) void coarsehead_pack_kernel(const PackP
         const int l = (int)(i / sq);
         i -= l * sq;
         const int r = (int)(i / Cpad), c = (int)(i % Cpad);
-        if (r < C && c < C) v = load_any(p.w[l], (int64_t)r * C + c, p.w_dtype[l]);
+        if (r < C && c < C) v = load1(p.w[l], (int64_t)r * C + c, p.w_dtype[l]);
     } else if (!p.backward) {                       // W3 [out][in]
         i -= 2 * sq;
         const int r = (int)(i / Cpad), c = (int)(i % Cpad);
-        if (r < KP && c < C) v = load_any(p.w[2], (int64_t)r * C + c, p.w_dtype[2]);
+        if (r < KP && c < C) v = load1(p.w[2], (int64_t)r * C + c, p.w_dtype[2]);
     } else if (i < 4 * sq) {                        // W1t, W2t [in][out]
         i -= 2 * sq;
         const int l = (int)(i / sq);
         i -= l * sq;
         const int r = (int)(i / Cpad), c = (int)(i % Cpad);
-        if (r < C && c < C) v = load_any(p.w[l], (int64_t)c * C + r, p.w_dtype[l]);
+        if (r < C && c < C) v = load1(p.w[l], (int64_t)c * C + r, p.w_dtype[l]);
     } else {                                        // W3t [in][out]
         i -= 4 * sq;
         const int r = (int)(i / Opad), c = (int)(i % Opad);
-        if (r < C && c < KP) v = load_any(p.w[2], (int64_t)c * C + r, p.w_dtype[2]);
+        if (r < C && c < KP) v = load1(p.w[2], (int64_t)c * C + r, p.w_dtype[2]);
     }
     ((typename El<DT>::type*)p.packed)[at] = down<DT>(v);
 }
@@ -412,7 +412,7 @@ bool bad_rows_count(int64_t rows, int32_t K) { return rows > ((INT64_C(1) << 31)
 const char* const CH_ENVELOPE = "coarsehead: C must be a multiple of 8 in 8..GDR_COARSEHEAD_MAX_C, K in 1..4, sh_dim one of 3, 12, 27, 48, "
                                 "K P <= GDR_COARSEHEAD_MAX_OUT and rows K below 2^31";
 
-int slabs_of(int64_t n) { return slabs_of(n, CH_SLAB_MIN, CH_MAX_SLABS); }
+int slabs_of(int64_t n) { return gdr::slabs_of(n, CH_SLAB_MIN, CH_MAX_SLABS); }
 
 struct FwdLds { int lda, sw; size_t region0, total; };
 FwdLds fwd_lds(int dtype, const Geo& g) {

@@ -27,8 +27,8 @@
 //   grad_bias: per-block column sums in f64, then one launch adds the partials in order and rounds once.
 // Tile sizes are an unmeasured choice.
 #include "gdr_common.h"
-#include "half_bits.h"
 #include "host_util.h"
+#include "row_io.h"
 #include "mfma_rows.h"
 
 namespace gdr {
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(CV_BLOCK) void conv3d_pack_kernel(const void* w, in
     const int CA = mirrored ? Cout : Cin, CB = mirrored ? Cin : Cout;
     const int ca = (int)(t % CA), cb = (int)((t / CA) % CB), kp = (int)(t / ((int64_t)CA * CB));
     const int co = mirrored ? ca : cb, ci = mirrored ? cb : ca, k = mirrored ? CV_TAPS - 1 - kp : kp;
-    ((typename El<DT>::type*)packed_)[t] = down<DT>(load_any(w, ((int64_t)co * Cin + ci) * CV_TAPS + k, w_dtype));
+    ((typename El<DT>::type*)packed_)[t] = down<DT>(load1(w, ((int64_t)co * Cin + ci) * CV_TAPS + k, w_dtype));
 }
 
 // ---- the product kernel ---------------------------------------------------------------------------------------------------------
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(CV_BLOCK) void conv3d_product_kernel(const ProdP p)
             typename El<DT>::acc sum = acc[j][i];
             if (p.bias) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) sum[e] += up<DT>(down<DT>(load_any(p.bias, co + e, p.bias_dtype)));
+                for (int e = 0; e < 4; ++e) sum[e] += up<DT>(down<DT>(load1(p.bias, co + e, p.bias_dtype)));
             }
             if (addend) {
                 const E* src = addend + row * p.CB + co;
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(CV_BLOCK) void conv3d_gw_fold_kernel(const P* part,
     const int ci = (int)(t % CI), co = (int)((t / CI) % CO), k = (int)(t / ((int64_t)CI * CO));
     P s = 0;
     for (int b = 0; b < slabs; ++b) s += part[(int64_t)b * total + t];
-    store_any(gw, ((int64_t)co * CI + ci) * CV_TAPS + k, gw_dtype, (float)s);
+    store1(gw, ((int64_t)co * CI + ci) * CV_TAPS + k, gw_dtype, (float)s);
 }
 
 // ---- grad_bias: per-block column sums, then one launch adds the partials in order -------------------------------------------
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(CV_BLOCK) void conv3d_bias_sum_kernel(const double*
     if (c >= C) return;
     double s = 0.0;
     for (int b = 0; b < blocks; ++b) s += part[(int64_t)b * C + c];
-    store_any(out, c, out_dtype, (float)s);
+    store1(out, c, out_dtype, (float)s);
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
@@ -313,10 +313,7 @@ int64_t voxels_of(int64_t B, int32_t D, int32_t H, int32_t W) {
     return n;
 }
 
-int slabs_of(int64_t n) {
-    const int64_t s = (n + CV_SLAB_MIN - 1) / CV_SLAB_MIN;
-    return s < 1 ? 1 : (s > CV_MAX_SLABS ? CV_MAX_SLABS : (int)s);
-}
+int slabs_of(int64_t n) { return gdr::slabs_of(n, CV_SLAB_MIN, CV_MAX_SLABS); }
 
 int bias_blocks_of(int64_t n) {
     const int64_t b = (n + 63) / 64;

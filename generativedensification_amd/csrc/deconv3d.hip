@@ -34,8 +34,8 @@
 //   column sums (grad_bias; grad_gamma / grad_beta from the partials): per-block partials in f64, one fold launch in block order.
 // No atomics.  Tile sizes are an unmeasured choice.
 #include "gdr_common.h"
-#include "half_bits.h"
 #include "host_util.h"
+#include "row_io.h"
 #include "mfma_rows.h"
 
 namespace gdr {
@@ -103,13 +103,13 @@ __device__ __forceinline__ void normalise(const uint4& raw, int c, double mean, 
     for (int e = 0; e < VE; ++e) {
         if constexpr (DT == GDR_NORM_F32) {
             double y = ((double)u.e[e] - mean) * rstd;
-            if (ln_w) y *= (double)load_any(ln_w, c + e, ln_w_dtype);
-            if (ln_b) y += (double)load_any(ln_b, c + e, ln_b_dtype);
+            if (ln_w) y *= (double)load1(ln_w, c + e, ln_w_dtype);
+            if (ln_b) y += (double)load1(ln_b, c + e, ln_b_dtype);
             dst[e] = y;
         } else {
             float y = (up<DT>(u.e[e]) - (float)mean) * (float)rstd;
-            if (ln_w) y *= load_any(ln_w, c + e, ln_w_dtype);
-            if (ln_b) y += load_any(ln_b, c + e, ln_b_dtype);
+            if (ln_w) y *= load1(ln_w, c + e, ln_w_dtype);
+            if (ln_b) y += load1(ln_b, c + e, ln_b_dtype);
             dst[e] = down<DT>(y);
         }
     }
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(DC_BLOCK) void deconv3d_pack_kernel(const void* w, 
     const int CA = transposed ? Cout : Cin, CB = transposed ? Cin : Cout;
     const int ca = (int)(i % CA), cb = (int)((i / CA) % CB), t = (int)(i / ((int64_t)CA * CB));
     const int ci = transposed ? cb : ca, co = transposed ? ca : cb;
-    ((typename El<DT>::type*)packed_)[i] = down<DT>(load_any(w, ((int64_t)ci * Cout + co) * DC_TAPS + t, w_dtype));
+    ((typename El<DT>::type*)packed_)[i] = down<DT>(load1(w, ((int64_t)ci * Cout + co) * DC_TAPS + t, w_dtype));
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(DC_BLOCK, 2) void deconv3d_forward_kernel(const Fwd
                 typename El<DT>::acc sum = acc[t][j][i];
                 if (p.bias) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) sum[e] += up<DT>(down<DT>(load_any(p.bias, co + e, p.bias_dtype)));
+                    for (int e = 0; e < 4; ++e) sum[e] += up<DT>(down<DT>(load1(p.bias, co + e, p.bias_dtype)));
                 }
                 float r[4];
 #pragma unroll
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(DC_BLOCK) void deconv3d_grad_input_kernel(const Gin
                     if (!(in && valid[i])) continue;
                     const T xh = ((T)up<DT>(X[(row0 + 16 * i + l16) * p.CI + c + e]) - mean[i]) * rstd[i];
                     const T gn = (T)acc[g][j][i][e];
-                    const T a = p.ln_w ? gn * (T)load_any(p.ln_w, c + e, p.ln_w_dtype) : gn;
+                    const T a = p.ln_w ? gn * (T)load1(p.ln_w, c + e, p.ln_w_dtype) : gn;
                     s1[i] += a;
                     s2[i] += a * xh;
                     pg[e] += gn * xh;
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(DC_BLOCK) void deconv3d_grad_input_kernel(const Gin
                 for (int e = 0; e < 4; ++e) {
                     const T xh = ((T)up<DT>(X[row * p.CI + c + e]) - mean[i]) * rstd[i];
                     const T gn = (T)acc[g][j][i][e];
-                    const T a = p.ln_w ? gn * (T)load_any(p.ln_w, c + e, p.ln_w_dtype) : gn;
+                    const T a = p.ln_w ? gn * (T)load1(p.ln_w, c + e, p.ln_w_dtype) : gn;
                     dst[e] = down<DT>((float)(rstd[i] * (a - s1[i] - xh * s2[i])));
                 }
             }
@@ -585,7 +585,7 @@ __global__ __launch_bounds__(DC_BLOCK) void deconv3d_gw_fold_kernel(const P* par
     const int co = (int)(i % CO), ci = (int)((i / CO) % CI), t = (int)(i / ((int64_t)CI * CO));
     P s = 0;
     for (int b = 0; b < slabs; ++b) s += part[(int64_t)b * total + i];
-    store_any(gw, ((int64_t)ci * CO + co) * DC_TAPS + t, gw_dtype, (float)s);
+    store1(gw, ((int64_t)ci * CO + co) * DC_TAPS + t, gw_dtype, (float)s);
 }
 
 // ---- column sums: per-block partials in f64, then one launch adds the partials in block order ------------------------------------
@@ -635,7 +635,7 @@ __global__ __launch_bounds__(DC_BLOCK) void deconv3d_colsum_fold_kernel(const Fo
     if (seg == 0 && c < p.C && p.out[y]) {
         double total = 0.0;
         for (int k = 0; k < DC_FOLD; ++k) total += sSeg[k][ch];
-        store_any(p.out[y], c, p.out_dtype[y], (float)total);
+        store1(p.out[y], c, p.out_dtype[y], (float)total);
     }
 }
 
@@ -655,10 +655,7 @@ int64_t rows_of(int64_t B, int32_t D, int32_t H, int32_t W) {
     return n;
 }
 
-int slabs_of(int64_t n) {
-    const int64_t s = (n + DC_SLAB_MIN - 1) / DC_SLAB_MIN;
-    return s < 1 ? 1 : (s > DC_MAX_SLABS ? DC_MAX_SLABS : (int)s);
-}
+int slabs_of(int64_t n) { return gdr::slabs_of(n, DC_SLAB_MIN, DC_MAX_SLABS); }
 
 int sum_blocks_of(int64_t rows) {
     const int64_t b = (rows + 63) / 64;

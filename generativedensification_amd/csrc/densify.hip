@@ -3,9 +3,9 @@
 //
 //   select   per segment b (rows ends[b - 1] .. ends[b] - 1, ends = the offsets clamped to [previous end, N]) the rows are
 //            ranked by descending value: NaN above every number, -0 = +0, equal values by ascending row.
-//              top-k  rank < k_b, k_b = ceil(round_dt(ratio * round_dt(n_b))) in f32 (the reference's
+//              top-k  rank < k_b, k_b = ceil(round_any(ratio * round_any(n_b))) in f32 (the reference's
 //                     (float(ratio) * num_nodes.to(x.dtype)).ceil()); k_b > n_b or not finite selects the whole segment
-//              top-p  round_dt(prefix_j) <= threshold, prefix_j the inclusive f32 sum of the segment's values in ranked order
+//              top-p  round_any(prefix_j) <= threshold, prefix_j the inclusive f32 sum of the segment's values in ranked order
 //            Rows at or behind ends[B - 1] are never selected.  new_offset = the cumulative number selected per segment.
 //   gate     forward out = feat (no mask) or feat * mask; backward dfeat = prob * g, dprob[i] = sum_c feat[i, c] * g[i, c] in f32.
 //   split    dest[i] = the number of rows before i on i's side of the mask; row i of coord / feat goes to row dest[i] of the
@@ -96,8 +96,6 @@ struct SelP {
 // the high bits of the orderable value that can differ: the f32 form of a bf16 has 16 zero bits below them, that of an f16 13
 __host__ __device__ __forceinline__ int value_bits(int dt) { return dt == GDR_NORM_F32 ? 32 : (dt == GDR_NORM_BF16 ? 16 : 19); }
 
-__device__ __forceinline__ float round_dt(float v, int dt) { return dt == GDR_NORM_F32 ? v : up_any(down_any(v, dt), dt); }
-
 // the number of segment ends <= pos: the segment of row / sorted position pos, B behind the last end (starts non-decreasing)
 __device__ __forceinline__ int seg_of(const int64_t* __restrict__ starts, int B, int64_t pos) {
     int lo = 0, hi = B;
@@ -123,8 +121,8 @@ __global__ __launch_bounds__(DN_FAN) void dn_segments_kernel(const SelP p) {
     int64_t kk = 0;
     if (t < p.B) {
         const int64_t n = end - start;
-        const float nr = round_dt((float)n, p.x_dt);
-        const float k = ceilf(round_dt(p.ratio * nr, p.x_dt));
+        const float nr = round_any((float)n, p.x_dt);
+        const float k = ceilf(round_any(p.ratio * nr, p.x_dt));
         kk = (k >= 0.f && k < 4.0e18f) ? (int64_t)k : n;       // (inf and NaN: the whole segment, as k > n)
         if (kk > n) kk = n;
         p.starts[t + 1] = end;
@@ -230,7 +228,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_topp_mask_kernel(const SelP p) {
     for (int q = 0; q < DN_ITEMS; ++q) {
         if (c.row[q] < 0) continue;
         const FV pre = join(carry, c.incl[q]);
-        p.mask[c.row[q]] = (c.seg[q] < p.B && round_dt(pre.v, p.x_dt) <= p.threshold) ? 1 : 0;
+        p.mask[c.row[q]] = (c.seg[q] < p.B && round_any(pre.v, p.x_dt) <= p.threshold) ? 1 : 0;
     }
 }
 
@@ -444,8 +442,6 @@ __global__ __launch_bounds__(DN_BLOCK) void dn_mask_dest_kernel(const uint8_t* _
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-int elem_bytes(int32_t dt) { return dt == GDR_NORM_F32 ? 4 : 2; }
-
 int check_rows(int64_t N, int64_t C) {
     if (N < 0) return invalid_arg("densify: N must be >= 0");
     if (N > DN_MAX_ROWS) return unsupported("densify: N must be at most 2^30");
@@ -511,7 +507,7 @@ int gdr_densify_select(const void* x, int32_t x_dtype, const int64_t* offset, in
     if (!(ratio > 0.f && ratio < 1.f)) return invalid_arg("densify_select: ratio must lie in (0, 1)");
     if (!(threshold >= 0.f && threshold <= 1.f)) return invalid_arg("densify_select: threshold must lie in [0, 1]");
     if (!offset || !new_offset || !workspace || (N && (!x || !mask))) return invalid_arg("densify_select: NULL argument");
-    if (misaligned(x, elem_bytes(x_dtype) - 1) || misaligned(offset, 7) || misaligned(new_offset, 7) || misaligned(workspace, 255))
+    if (misaligned(x, esize(x_dtype) - 1) || misaligned(offset, 7) || misaligned(new_offset, 7) || misaligned(workspace, 255))
         return invalid_arg("densify_select: unaligned buffer");
     const SelWs ws = select_workspace(N, B);
     if (workspace_bytes < ws.bytes) return workspace_too_small("densify_select: workspace smaller than gdr_densify_select_bytes");
@@ -651,8 +647,8 @@ int gdr_densify_rows_backward(const uint8_t* mask, const int64_t* dest, int64_t 
         return invalid_arg("densify_rows_backward: NULL argument");
     const unsigned cm = (unsigned)coord_elem_bytes - 1;
     if ((feat && bad_rows(feat, feat_stride, C)) || bad_rows(grad_sel, grad_stride, C) || bad_rows(grad_rest, grad_stride, C) ||
-        misaligned(grad_feat, 15) || misaligned(dest, 7) || misaligned(prob, prob ? elem_bytes(prob_dtype) - 1 : 0) ||
-        misaligned(grad_prob, prob ? elem_bytes(prob_dtype) - 1 : 0) || misaligned(gcoord_sel, cm) || misaligned(gcoord_rest, cm) ||
+        misaligned(grad_feat, 15) || misaligned(dest, 7) || misaligned(prob, prob ? esize(prob_dtype) - 1 : 0) ||
+        misaligned(grad_prob, prob ? esize(prob_dtype) - 1 : 0) || misaligned(gcoord_sel, cm) || misaligned(gcoord_rest, cm) ||
         misaligned(grad_coord, cm))
         return invalid_arg("densify_rows_backward: rows must start on 16 bytes with a stride that is a multiple of 8 and at least C");
     RowP p = {};

@@ -36,8 +36,8 @@
 // tile bookkeeping, the fold, the backward's LDS carve) is head_rows.h.
 // Tile sizes, the step, the slab length and where the weights sit are unmeasured choices.
 #include "gdr_common.h"
-#include "half_bits.h"
 #include "host_util.h"
+#include "row_io.h"
 #include "mfma_rows.h"
 #include "head_rows.h"
 
@@ -103,19 +103,19 @@ __global__ __launch_bounds__(HEAD_BLOCK) void finehead_pack_kernel(const PackP p
     float v = 0.0f;
     if (i < sq) {                                   // W1 [out][in]
         const int r = (int)(i / Cpad), c = (int)(i % Cpad);
-        if (r < C && c < C) v = load_any(p.w[0], (int64_t)r * C + c, p.w_dtype[0]);
+        if (r < C && c < C) v = load1(p.w[0], (int64_t)r * C + c, p.w_dtype[0]);
     } else if (!p.backward) {                       // W2 [out][in]
         i -= sq;
         const int r = (int)(i / Cpad), c = (int)(i % Cpad);
-        if (r < P && c < C) v = load_any(p.w[1], (int64_t)r * C + c, p.w_dtype[1]);
+        if (r < P && c < C) v = load1(p.w[1], (int64_t)r * C + c, p.w_dtype[1]);
     } else if (i < 2 * sq) {                        // W1t [in][out]
         i -= sq;
         const int r = (int)(i / Cpad), c = (int)(i % Cpad);
-        if (r < C && c < C) v = load_any(p.w[0], (int64_t)c * C + r, p.w_dtype[0]);
+        if (r < C && c < C) v = load1(p.w[0], (int64_t)c * C + r, p.w_dtype[0]);
     } else {                                        // W2t [in][out]
         i -= 2 * sq;
         const int r = (int)(i / Opad), c = (int)(i % Opad);
-        if (r < C && c < P) v = load_any(p.w[1], (int64_t)c * C + r, p.w_dtype[1]);
+        if (r < C && c < P) v = load1(p.w[1], (int64_t)c * C + r, p.w_dtype[1]);
     }
     ((typename El<DT>::type*)p.packed)[at] = down<DT>(v);
 }
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(HEAD_BLOCK) void finehead_forward_kernel(const FwdP
             const int j = 16 * jt + 4 * quad + e;
             if (row >= p.n || j >= g.P) continue;
             const T v = (T)v2[e] + bias_at<DT>(p.b[1], p.b_dtype[1], j, g.P);
-            store_any(p.out, row * g.P + j, p.out_dtype, (float)v);
+            store1(p.out, row * g.P + j, p.out_dtype, (float)v);
         }
     }
 }
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(HEAD_BLOCK) void finehead_backward_kernel(const Bwd
             const int64_t base = r0 * P;
             for (int i = tid; i < step * P; i += HEAD_BLOCK) {
                 const int r = i / P, j = i - r * P;
-                const E e = down<DT>(i < count && p.gout ? load_any(p.gout, base + i, p.gout_dtype) : 0.0f);
+                const E e = down<DT>(i < count && p.gout ? load1(p.gout, base + i, p.gout_dtype) : 0.0f);
                 RZ[r * ldz + j] = e;
                 gT[j * ldt + r] = e;
             }
@@ -424,7 +424,7 @@ __device__ __forceinline__ float assembled(const AsmP& p, int k, int w, int64_t 
         while (row >= p.start[l + 1]) ++l;
         const int64_t rr = row - p.start[l];
         if (k == 0) return p.coord[l][rr * 3 + col];
-        const float v = load_any(p.attr[l], rr * p.P + column_of(k, p.sh) + col, p.attr_dtype);
+        const float v = load1(p.attr[l], rr * p.P + column_of(k, p.sh) + col, p.attr_dtype);
         return k == 2 ? v + p.opacity_shift : (k == 3 ? v + p.scaling_shift : v);
     }
     const int64_t m = p.masked_of_rest[row - L];
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(HEAD_BLOCK) void finehead_assemble_backward_kernel(
             } else if (p.gattr[l]) {
                 const int k = c < p.sh ? 1 : (c == p.sh ? 2 : (c < p.sh + 4 ? 3 : 4));
                 const int wk = width_of(k, p.sh);
-                store_any(p.gattr[l], rr * p.P + c, p.attr_dtype, p.g[k] ? p.g[k][row * wk + c - column_of(k, p.sh)] : 0.0f);
+                store1(p.gattr[l], rr * p.P + c, p.attr_dtype, p.g[k] ? p.g[k][row * wk + c - column_of(k, p.sh)] : 0.0f);
             }
         } else if (s < 6) {                           // a coarse tensor
             const int k = s == 2 ? 0 : s - 1;
@@ -512,7 +512,7 @@ bool bad_rows_count(int64_t rows) { return rows > (INT64_C(1) << 31) - 1; }
 
 const char* const FH_ENVELOPE = "finehead: C must be a multiple of 8 in 8..GDR_FINEHEAD_MAX_C, sh_dim one of 3, 12, 27, 48 and rows below 2^31";
 
-int slabs_of(int64_t n) { return slabs_of(n, FH_SLAB_MIN, FH_MAX_SLABS); }
+int slabs_of(int64_t n) { return gdr::slabs_of(n, FH_SLAB_MIN, FH_MAX_SLABS); }
 
 struct FwdLds { int lda; size_t total; };
 FwdLds fwd_lds(int dtype, const Geo& g) {

@@ -51,35 +51,6 @@ struct GaP {
     float scale;
 };
 
-// DH elements from / to element index idx, a multiple of 8 from a 16-byte aligned base
-template <int DH>
-__device__ __forceinline__ void loadh(const void* base, int64_t idx, int dt, float (&x)[DH]) {
-#pragma unroll
-    for (int c = 0; c < DH / 8; ++c) {
-        float y[8];
-        load8(base, idx + 8 * c, dt, y);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[8 * c + e] = y[e];
-    }
-}
-template <int DH>
-__device__ __forceinline__ void storeh(void* base, int64_t idx, int dt, const float (&x)[DH]) {
-#pragma unroll
-    for (int c = 0; c < DH / 8; ++c) {
-        float y[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) y[e] = x[8 * c + e];
-        store8(base, idx + 8 * c, dt, y);
-    }
-}
-template <int DH>
-__device__ __forceinline__ float dot(const float (&a)[DH], const float (&b)[DH]) {
-    float s = a[0] * b[0];
-#pragma unroll
-    for (int e = 1; e < DH; ++e) s = fmaf(a[e], b[e], s);
-    return s;
-}
-
 // a query row times scale, once: the score is then a plain dot product, every site gives the same bits and s - max is exactly
 // 0 at the maximum (scale * dot(q, k) - max would be contracted into fma(scale, dot, -max), which returns the rounding residual
 // of the product instead); dk = sum ds * (scale q) takes the same row
@@ -97,12 +68,12 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_fwd_kernel(const GaP p) {
     const int col = (int)(idx - row * p.H) * DH, Lk = p.Lk;
     const int64_t krow = row / p.Lq * Lk;
     float q[DH], c[DH], u[DH];
-    loadh<DH>(p.q, row * p.q_stride + col, p.q_dt, q);
+    load_row<DH>(p.q, row * p.q_stride + col, p.q_dt, q);
     scaled<DH>(q, p.scale);
     float mx = -INFINITY;
 #pragma unroll 1
     for (int j = 0; j < Lk; ++j) {
-        loadh<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
+        load_row<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
         mx = fmaxf(mx, dot<DH>(q, c));
     }
     float l = 0.f;
@@ -110,17 +81,17 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_fwd_kernel(const GaP p) {
     for (int e = 0; e < DH; ++e) u[e] = 0.f;
 #pragma unroll 1
     for (int j = 0; j < Lk; ++j) {
-        loadh<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
+        load_row<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
         const float ex = expf(dot<DH>(q, c) - mx);
         l += ex;
-        loadh<DH>(p.v, (krow + j) * p.v_stride + col, p.v_dt, c);
+        load_row<DH>(p.v, (krow + j) * p.v_stride + col, p.v_dt, c);
 #pragma unroll
         for (int e = 0; e < DH; ++e) u[e] = fmaf(ex, c[e], u[e]);
     }
     const float inv = 1.0f / l;
 #pragma unroll
     for (int e = 0; e < DH; ++e) u[e] *= inv;
-    storeh<DH>(p.out, row * ((int64_t)p.H * DH) + col, p.out_dt, u);
+    store_row<DH>(p.out, row * ((int64_t)p.H * DH) + col, p.out_dt, u);
 }
 
 template <int DH>
@@ -134,27 +105,27 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_bwd_kernel(const GaP p) {
         const int u = t / qi, r = t - u * qi, i = r / H, col = (r - i * H) * DH;
         const int64_t row = (m0 + u) * Lq + i, krow = (m0 + u) * Lk;
         float q[DH], g[DH], c[DH], dq[DH];
-        loadh<DH>(p.q, row * p.q_stride + col, p.q_dt, q);
-        loadh<DH>(p.grad, row * p.grad_stride + col, p.grad_dt, g);
+        load_row<DH>(p.q, row * p.q_stride + col, p.q_dt, q);
+        load_row<DH>(p.grad, row * p.grad_stride + col, p.grad_dt, g);
         scaled<DH>(q, p.scale);
         float mx = -INFINITY, pivot = 0.f;
 #pragma unroll 1
         for (int j = 0; j < Lk; ++j) {
-            loadh<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
+            load_row<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
             const float s = dot<DH>(q, c);
             if (s > mx) {
                 mx = s;
-                loadh<DH>(p.v, (krow + j) * p.v_stride + col, p.v_dt, c);
+                load_row<DH>(p.v, (krow + j) * p.v_stride + col, p.v_dt, c);
                 pivot = dot<DH>(g, c);
             }
         }
         float l = 0.f, a = 0.f;
 #pragma unroll 1
         for (int j = 0; j < Lk; ++j) {
-            loadh<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
+            load_row<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
             const float ex = expf(dot<DH>(q, c) - mx);
             l += ex;
-            loadh<DH>(p.v, (krow + j) * p.v_stride + col, p.v_dt, c);
+            load_row<DH>(p.v, (krow + j) * p.v_stride + col, p.v_dt, c);
             a = fmaf(ex, dot<DH>(g, c) - pivot, a);
         }
         const float inv = 1.0f / l, mean = a * inv;
@@ -162,9 +133,9 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_bwd_kernel(const GaP p) {
         for (int e = 0; e < DH; ++e) dq[e] = 0.f;
 #pragma unroll 1
         for (int j = 0; j < Lk; ++j) {
-            loadh<DH>(p.v, (krow + j) * p.v_stride + col, p.v_dt, c);
+            load_row<DH>(p.v, (krow + j) * p.v_stride + col, p.v_dt, c);
             const float dp = dot<DH>(g, c);
-            loadh<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
+            load_row<DH>(p.k, (krow + j) * p.k_stride + col, p.k_dt, c);
             const float pv = expf(dot<DH>(q, c) - mx) * inv;
             const float ds = pv * ((dp - pivot) - mean);
 #pragma unroll
@@ -172,7 +143,7 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_bwd_kernel(const GaP p) {
         }
 #pragma unroll
         for (int e = 0; e < DH; ++e) dq[e] *= p.scale;
-        storeh<DH>(p.dq, row * E + col, p.q_dt, dq);
+        store_row<DH>(p.dq, row * E + col, p.q_dt, dq);
         rec[t] = make_float4(mx, inv, pivot, mean);
     }
     __syncthreads();
@@ -181,8 +152,8 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_bwd_kernel(const GaP p) {
         const int u = t / ki, r = t - u * ki, j = r / H, h = r - j * H, col = h * DH;
         const int64_t row0 = (m0 + u) * Lq, krow = (m0 + u) * Lk + j;
         float c[DH], w[DH], q[DH], g[DH], dk[DH], dv[DH];
-        loadh<DH>(p.k, krow * p.k_stride + col, p.k_dt, c);
-        loadh<DH>(p.v, krow * p.v_stride + col, p.v_dt, w);
+        load_row<DH>(p.k, krow * p.k_stride + col, p.k_dt, c);
+        load_row<DH>(p.v, krow * p.v_stride + col, p.v_dt, w);
 #pragma unroll
         for (int e = 0; e < DH; ++e) dk[e] = dv[e] = 0.f;
         // blocks of GA_SUM queries are summed on their own and then added: a chain of 64 additions onto one growing sum
@@ -195,8 +166,8 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_bwd_kernel(const GaP p) {
             for (int e = 0; e < DH; ++e) bk[e] = bv[e] = 0.f;
 #pragma unroll 1
             for (int i = i0; i < i1; ++i) {
-                loadh<DH>(p.q, (row0 + i) * p.q_stride + col, p.q_dt, q);
-                loadh<DH>(p.grad, (row0 + i) * p.grad_stride + col, p.grad_dt, g);
+                load_row<DH>(p.q, (row0 + i) * p.q_stride + col, p.q_dt, q);
+                load_row<DH>(p.grad, (row0 + i) * p.grad_stride + col, p.grad_dt, g);
                 scaled<DH>(q, p.scale);
                 const float4 st = rec[(u * Lq + i) * H + h];
                 const float pv = expf(dot<DH>(q, c) - st.x) * st.y;
@@ -210,8 +181,8 @@ __global__ __launch_bounds__(GA_BLOCK) void groupattn_bwd_kernel(const GaP p) {
 #pragma unroll
             for (int e = 0; e < DH; ++e) { dk[e] += bk[e]; dv[e] += bv[e]; }
         }
-        storeh<DH>(p.dk, krow * E + col, p.k_dt, dk);
-        storeh<DH>(p.dv, krow * E + col, p.v_dt, dv);
+        store_row<DH>(p.dk, krow * E + col, p.k_dt, dk);
+        store_row<DH>(p.dv, krow * E + col, p.v_dt, dv);
     }
 }
 

@@ -5,7 +5,7 @@
 // the fold kernel.  Host side: the backward's LDS carve, the slab count, the dtype dispatch and the fold's launch.
 // What differs between the heads stays in their files: the layer count and the activations, the packed and partial layouts,
 // the epilogues, the backward's step sequence.  Nothing here asks which head is calling.
-// Include after gdr_common.h, half_bits.h, host_util.h and mfma_rows.h.
+// Include after gdr_common.h, host_util.h, row_io.h and mfma_rows.h.
 #pragma once
 #include <stdio.h>
 
@@ -48,7 +48,7 @@ __device__ __forceinline__ void tile_mma(const typename El<DT>::type* A, int lda
 
 // a bias as the forward adds it: rounded to the compute dtype; 0 beyond its n entries
 template <int DT> __device__ __forceinline__ Sc<DT> bias_at(const void* b, int dt, int c, int n) {
-    return c < n ? (Sc<DT>)up<DT>(down<DT>(load_any(b, c, dt))) : (Sc<DT>)0;
+    return c < n ? (Sc<DT>)up<DT>(down<DT>(load1(b, c, dt))) : (Sc<DT>)0;
 }
 
 // 4 consecutive elements of an LDS / global row
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(HEAD_BLOCK) void head_fold_kernel(const FoldP p) {
     for (int k = 0; k < 6; ++k) {
         if (k >= p.count) return;
         if (i < p.size[k]) {
-            if (p.out[k]) store_any(p.out[k], i, p.out_dtype[k], (float)sum);
+            if (p.out[k]) store1(p.out[k], i, p.out_dtype[k], (float)sum);
             return;
         }
         i -= p.size[k];
@@ -189,12 +189,6 @@ __global__ __launch_bounds__(HEAD_BLOCK) void head_fold_kernel(const FoldP p) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-// one slab of rows per slab_min, max_slabs at most
-int slabs_of(int64_t n, int slab_min, int max_slabs) {
-    const int64_t s = (n + slab_min - 1) / slab_min;
-    return s < 1 ? 1 : (s > max_slabs ? max_slabs : (int)s);
-}
-
 // the LDS of a backward step: two Cpad-wide and one Opad-wide row buffers, then `nt` transposed buffers of Cpad channels and
 // one of Opad
 struct BwdLds { int step, lda, ldz, ldt; size_t total; };

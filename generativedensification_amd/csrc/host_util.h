@@ -34,11 +34,17 @@ static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a
 // mask = alignment in bytes - 1; a NULL pointer is aligned
 static inline bool misaligned(const void* p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
 
-// a storage type code of the row kernels (GDR_NORM_F16 / BF16 / F32)
-static inline bool bad_dtype(int32_t dt) { return dt < GDR_NORM_F16 || dt > GDR_NORM_F32; }
-static inline size_t esize(int32_t dt) { return dt == GDR_NORM_F32 ? 4 : 2; }      // the bytes of one element
+// a storage type code (GDR_F16 / GDR_BF16 / GDR_F32)
+static inline bool bad_dtype(int32_t dt) { return dt < GDR_F16 || dt > GDR_F32; }
+static inline size_t esize(int32_t dt) { return dt == GDR_F32 ? 4 : 2; }      // the bytes of one element
 
 // a (rows, C) matrix read or written in 8-element pieces: 16-byte base, a stride that is a multiple of 8 and at least C
 static inline bool bad_rows(const void* ptr, int64_t stride, int64_t C) { return misaligned(ptr, 15) || stride < C || stride % 8; }
+
+// the slabs a partial sum over n rows is cut into: one per slab_min rows, max_slabs at most
+static inline int slabs_of(int64_t n, int slab_min, int max_slabs) {
+    const int64_t s = (n + slab_min - 1) / slab_min;
+    return s < 1 ? 1 : (s > max_slabs ? max_slabs : (int)s);
+}
 
 }  // namespace gdr

@@ -32,6 +32,8 @@ __device__ __forceinline__ void fill_row(float (&x)[K][8], float val) {
         for (int v = 0; v < 8; ++v) x[k][v] = val;
 }
 
+using gdr::load_row;    // (row_io.h's row of one lane stays visible beside this one)
+
 // the lane's pieces of the row that starts at element `off` of base (a multiple of 8); pieces that are off hold zeros
 template <int K>
 __device__ __forceinline__ void load_row(const void* base, int64_t off, int dt, const bool (&on)[K], int l, int lc, float (&x)[K][8]) {

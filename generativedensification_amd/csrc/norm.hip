@@ -105,8 +105,8 @@ int gdr_norm_pe_forward(const void* x, int32_t x_dtype, const void* feat, int64_
     if (!(eps >= 0.f)) return invalid_arg("norm_pe_forward: eps must be >= 0");
     if (P == 0) return GDR_OK;
     if (!x || !feat || !freq || !out) return invalid_arg("norm_pe_forward: NULL argument");
-    if (bad_rows(feat, feat_stride, C) || bad_rows(out, out_stride, 6 * F + C) || misaligned(x, elem_bytes(x_dtype) - 1) ||
-        misaligned(freq, elem_bytes(freq_dtype) - 1))
+    if (bad_rows(feat, feat_stride, C) || bad_rows(out, out_stride, 6 * F + C) || misaligned(x, esize(x_dtype) - 1) ||
+        misaligned(freq, esize(freq_dtype) - 1))
         return invalid_arg("norm_pe_forward: rows must start on 16 bytes with a stride that is a multiple of 8 and covers the row");
     PeP p = {};
     p.x = x; p.feat = feat; p.freq = freq; p.out = out;
@@ -126,9 +126,9 @@ int gdr_norm_pe_backward(const void* grad_out, int64_t grad_stride, int32_t grad
     if (P == 0) return GDR_OK;
     if (!x || !feat || !freq || !grad_out) return invalid_arg("norm_pe_backward: NULL argument");
     const int W = 6 * F + C;
-    const unsigned gmask = 2 * elem_bytes(grad_dtype) - 1;
-    if (bad_rows(feat, feat_stride, C) || misaligned(grad_feat, 15) || misaligned(x, elem_bytes(x_dtype) - 1) ||
-        misaligned(grad_x, elem_bytes(x_dtype) - 1) || misaligned(freq, elem_bytes(freq_dtype) - 1) || grad_stride < W ||
+    const unsigned gmask = 2 * esize(grad_dtype) - 1;
+    if (bad_rows(feat, feat_stride, C) || misaligned(grad_feat, 15) || misaligned(x, esize(x_dtype) - 1) ||
+        misaligned(grad_x, esize(x_dtype) - 1) || misaligned(freq, esize(freq_dtype) - 1) || grad_stride < W ||
         grad_stride % 2 || misaligned(grad_out, gmask))
         return invalid_arg("norm_pe_backward: feat rows must start on 16 bytes with a stride that is a multiple of 8; grad_out "
                            "rows on two elements with an even stride that covers the row");

@@ -37,8 +37,6 @@ __device__ __forceinline__ void load2(const void* base, int64_t idx, int dt, flo
         a = up_any((uint16_t)(v & 0xffffu), dt); b = up_any((uint16_t)(v >> 16), dt);
     }
 }
-// v as an element of storage type dt holds it
-__device__ __forceinline__ float round_any(float v, int dt) { return dt == GDR_NORM_F32 ? v : up_any(down_any(v, dt), dt); }
 
 __device__ __forceinline__ int64_t clamp_end(const int64_t* __restrict__ offset, int i, int64_t N) {
     const int64_t v = offset[i];
@@ -443,8 +441,6 @@ __global__ __launch_bounds__(NM_BLOCK) void pe_bwd_kernel(const PeP p) {
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 constexpr int64_t NM_MAX_ROWS = INT64_C(0x7fffffff);
-
-int elem_bytes(int32_t dt) { return dt == GDR_NORM_F32 ? 4 : 2; }
 
 // 0, or the status with the message set
 int check_channels(int64_t C) {

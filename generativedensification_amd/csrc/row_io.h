@@ -1,18 +1,32 @@
-// row_io.h — elements of a runtime storage type (GDR_NORM_F16 / BF16 / F32) <-> f32 on the device, the lane-group row sum and
-// the LayerNorm statistics of a row held by a lane group, as norm.hip, densify.hip, viewattn.hip, groupattn.hip and volcond.hip
-// use them; ln_rows.h builds the rest of what the three row LayerNorms share on top of this (internal; include after
-// gdr_common.h).
+// row_io.h — elements and rows of a run-time storage type (GDR_F16 / GDR_BF16 / GDR_F32) <-> f32 on the device: one element
+// (load1 / store1: every row kernel and, through mfma_rows.h, the weights, biases and partial sums of conv3d.hip, deconv3d.hip,
+// coarsehead.hip and finehead.hip), eight (load8 / store8: norm.hip, densify.hip, volcond.hip, upscale.hip and ln_rows.h), a
+// head's row (load_row / store_row / dot: viewattn.hip, groupattn.hip and the gather form of attn.hip); then the lane-group
+// row sum and the LayerNorm statistics of a row held by a lane group, on which ln_rows.h builds the rest of what the row
+// LayerNorms share (internal; include after gdr_common.h).  A new module takes these from here.
 #pragma once
 #include "half_bits.h"
 
 namespace gdr {
 
-__device__ __forceinline__ float up_any(uint16_t b, int dt) { return dt == GDR_NORM_BF16 ? up16<true>(b) : up16<false>(b); }
-__device__ __forceinline__ uint16_t down_any(float f, int dt) { return dt == GDR_NORM_BF16 ? down16<true>(f) : down16<false>(f); }
+// one element.  (up_any / down_any written out: called as functions here, the compiler lays out the MFMA kernels' bias and
+// weight loops differently, and those are the kernels whose time was tuned)
+__device__ __forceinline__ float load1(const void* base, int64_t idx, int dt) {
+    if (dt == GDR_F32) return ((const float*)base)[idx];
+    const uint16_t b = ((const uint16_t*)base)[idx];
+    return dt == GDR_BF16 ? up16<true>(b) : up16<false>(b);
+}
+__device__ __forceinline__ void store1(void* base, int64_t idx, int dt, float x) {
+    if (dt == GDR_F32) ((float*)base)[idx] = x;
+    else ((uint16_t*)base)[idx] = dt == GDR_BF16 ? down16<true>(x) : down16<false>(x);
+}
 
-// idx: an element index that is a multiple of 8 from a 16-byte aligned base
+// idx: an element index that is a multiple of 8 from a 16-byte aligned base.  The dtype is picked per element, not once
+// around half_bits.h's unpack8 / pack8: that form gives the same bits, but the compiler then keeps both conversions of a row
+// alive across the branch, and five row kernels (ada_bwd<2>, rowmap_norm_bwd<2>, modln_bwd<1>, sample_fwd,
+// viewattn_fwd_many<16>) lose a wave per SIMD to the extra registers (EXPERIMENTS.md, typed rows).
 __device__ __forceinline__ void load8(const void* base, int64_t idx, int dt, float (&x)[8]) {
-    if (dt == GDR_NORM_F32) {
+    if (dt == GDR_F32) {
         const float4* p = reinterpret_cast<const float4*>((const float*)base + idx);
         const float4 a = p[0], b = p[1];
         x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
@@ -24,7 +38,7 @@ __device__ __forceinline__ void load8(const void* base, int64_t idx, int dt, flo
     }
 }
 __device__ __forceinline__ void store8(void* base, int64_t idx, int dt, const float (&x)[8]) {
-    if (dt == GDR_NORM_F32) {
+    if (dt == GDR_F32) {
         float4* p = reinterpret_cast<float4*>((float*)base + idx);
         p[0] = make_float4(x[0], x[1], x[2], x[3]);
         p[1] = make_float4(x[4], x[5], x[6], x[7]);
@@ -35,12 +49,61 @@ __device__ __forceinline__ void store8(void* base, int64_t idx, int dt, const fl
         *reinterpret_cast<uint4*>((uint16_t*)base + idx) = u.raw;
     }
 }
-__device__ __forceinline__ float load1(const void* base, int64_t idx, int dt) {
-    return dt == GDR_NORM_F32 ? ((const float*)base)[idx] : up_any(((const uint16_t*)base)[idx], dt);
+
+// N = 4 or a multiple of 8 elements from / to element index idx, a multiple of min(N, 8) from a 16-byte aligned base
+template <int N>
+__device__ __forceinline__ void load_row(const void* base, int64_t idx, int dt, float (&x)[N]) {
+    static_assert(N == 4 || N % 8 == 0, "a row is 4 or a multiple of 8 elements");
+    if constexpr (N == 4) {
+        if (dt == GDR_F32) {
+            const float4 a = *reinterpret_cast<const float4*>((const float*)base + idx);
+            x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
+        } else {
+            union { uint2 raw; uint16_t e[4]; } u;
+            u.raw = *reinterpret_cast<const uint2*>((const uint16_t*)base + idx);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[k] = up_any(u.e[k], dt);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < N / 8; ++q) {
+            float y[8];
+            load8(base, idx + 8 * q, dt, y);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[8 * q + k] = y[k];
+        }
+    }
 }
-__device__ __forceinline__ void store1(void* base, int64_t idx, int dt, float x) {
-    if (dt == GDR_NORM_F32) ((float*)base)[idx] = x;
-    else ((uint16_t*)base)[idx] = down_any(x, dt);
+template <int N>
+__device__ __forceinline__ void store_row(void* base, int64_t idx, int dt, const float (&x)[N]) {
+    static_assert(N == 4 || N % 8 == 0, "a row is 4 or a multiple of 8 elements");
+    if constexpr (N == 4) {
+        if (dt == GDR_F32) {
+            *reinterpret_cast<float4*>((float*)base + idx) = make_float4(x[0], x[1], x[2], x[3]);
+        } else {
+            union { uint2 raw; uint16_t e[4]; } u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) u.e[k] = down_any(x[k], dt);
+            *reinterpret_cast<uint2*>((uint16_t*)base + idx) = u.raw;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < N / 8; ++q) {
+            float y[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) y[k] = x[8 * q + k];
+            store8(base, idx + 8 * q, dt, y);
+        }
+    }
+}
+
+// <a, b> as one fma chain in ascending order
+template <int N>
+__device__ __forceinline__ float dot(const float (&a)[N], const float (&b)[N]) {
+    float s = a[0] * b[0];
+#pragma unroll
+    for (int k = 1; k < N; ++k) s = fmaf(a[k], b[k], s);
+    return s;
 }
 
 // the sum over the LC lanes of a group, the same bits in every lane (lc = LC)

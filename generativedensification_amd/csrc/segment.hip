@@ -46,17 +46,16 @@ template <> struct Tr<GDR_SEG_BF16> { using Elem = uint16_t; using Acc = float; 
 template <> struct Tr<GDR_SEG_F32>  { using Elem = float;    using Acc = float;   static constexpr int VFULL = 4; };
 template <> struct Tr<GDR_SEG_I64>  { using Elem = int64_t;  using Acc = int64_t; static constexpr int VFULL = 2; };
 
+// half_bits.h's conversions, and an i64 as it is
 template <int KIND>
 __device__ __forceinline__ typename Tr<KIND>::Acc up(typename Tr<KIND>::Elem e) {
-    if constexpr (KIND == GDR_SEG_F16) return up16<false>(e);
-    else if constexpr (KIND == GDR_SEG_BF16) return up16<true>(e);
-    else return e;
+    if constexpr (KIND == GDR_SEG_I64) return e;
+    else return gdr::up<KIND>(e);
 }
 template <int KIND>
 __device__ __forceinline__ typename Tr<KIND>::Elem down(typename Tr<KIND>::Acc a) {
-    if constexpr (KIND == GDR_SEG_F16) return down16<false>(a);
-    else if constexpr (KIND == GDR_SEG_BF16) return down16<true>(a);
-    else return a;
+    if constexpr (KIND == GDR_SEG_I64) return a;
+    else return gdr::down<KIND>(a);
 }
 
 // V elements at p: one 16-byte access when V is the full vector, one element when V = 1

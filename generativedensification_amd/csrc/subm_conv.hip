@@ -28,8 +28,6 @@
 //   G is kept in `planes` words of the operand type whose sum is the f32 sum (1 for f32, 2 for f16, 3 for bf16): with one
 //     site per voxel the further planes are zero, with several the 16-bit MFMA still sees the f32 sum.
 // Tile sizes are an unmeasured choice.
-#include <type_traits>
-
 #include "gdr_common.h"
 #include "half_bits.h"
 #include "host_util.h"
@@ -49,21 +47,9 @@ using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 // DT: GDR_SUBM_F16, GDR_SUBM_BF16, GDR_SUBM_F32
-template <int DT> struct El {
-    using type = typename std::conditional<DT == GDR_SUBM_F32, float, uint16_t>::type;
-    static constexpr int VE = 16 / (int)sizeof(type);                       // elements per 16-byte vector
+template <int DT> struct El : Stored<DT> {
     static constexpr int PLANES = DT == GDR_SUBM_F32 ? 1 : (DT == GDR_SUBM_F16 ? 2 : 3);
 };
-
-template <int DT> __device__ __forceinline__ float up(typename El<DT>::type v) {
-    if constexpr (DT == GDR_SUBM_F32) return v;
-    else return up16<DT == GDR_SUBM_BF16>(v);
-}
-
-template <int DT> __device__ __forceinline__ typename El<DT>::type down(float f) {   // round to nearest even
-    if constexpr (DT == GDR_SUBM_F32) return f;
-    else return down16<DT == GDR_SUBM_BF16>(f);
-}
 
 // VE elements from global memory as one 16-byte vector (vec) or one by one
 template <int DT> __device__ __forceinline__ uint4 load_vec(const typename El<DT>::type* p, int vec) {
@@ -427,7 +413,6 @@ const char* subm_check(const gdr_subm_args* a) {
     return nullptr;
 }
 
-size_t subm_esize(int dtype) { return dtype == GDR_SUBM_F32 ? 4 : 2; }
 int planes_of(int dtype) { return dtype == GDR_SUBM_F32 ? 1 : (dtype == GDR_SUBM_F16 ? 2 : 3); }
 
 struct BwdWs { size_t G, wt, part, bytes; };
@@ -435,15 +420,15 @@ struct BwdWs { size_t G, wt, part, bytes; };
 BwdWs bwd_workspace(const gdr_subm_args* a) {
     BwdWs w;
     size_t at = 0;
-    w.G = at; at += align_up((size_t)planes_of(a->dtype) * (size_t)a->N * a->Cout * subm_esize(a->dtype));
-    w.wt = at; at += align_up((size_t)a->K * a->Cin * a->Cout * subm_esize(a->dtype));
+    w.G = at; at += align_up((size_t)planes_of(a->dtype) * (size_t)a->N * a->Cout * esize(a->dtype));
+    w.wt = at; at += align_up((size_t)a->K * a->Cin * a->Cout * esize(a->dtype));
     w.part = at; at += align_up((size_t)SC_BIAS_BLOCKS * a->Cout * sizeof(float));
     w.bytes = at;
     return w;
 }
 
 int row_vec(const void* ptr, int64_t stride, int dtype) {
-    return !((uintptr_t)ptr & 15u) && (stride * (int64_t)subm_esize(dtype)) % 16 == 0;
+    return !((uintptr_t)ptr & 15u) && (stride * (int64_t)esize(dtype)) % 16 == 0;
 }
 
 #define GDR_SUBM_DT(KERNEL, ...)                                                                          \
@@ -526,7 +511,7 @@ int gdr_subm_conv_forward(const gdr_subm_args* a, const void* feat, int64_t feat
     if (a->N == 0) return GDR_OK;
     if (!feat || !nbr || !weight || !out) return invalid_arg("subm_conv_forward: NULL argument");
     if (feat_stride < a->Cin) return invalid_arg("subm_conv_forward: feature row stride smaller than Cin");
-    const size_t es = subm_esize(a->dtype);
+    const size_t es = esize(a->dtype);
     if (misaligned(feat, es - 1) || misaligned(bias, es - 1) || misaligned(weight, 15) || misaligned(out, 15) ||
         misaligned(nbr, 3))
         return invalid_arg("subm_conv_forward: unaligned buffer");
@@ -549,7 +534,7 @@ int gdr_subm_conv_backward(const gdr_subm_args* a, const void* grad_out, const v
     if (const char* why = subm_check(a)) return invalid_arg(why);
     if (a->N == 0) return GDR_OK;
     if (!grad_feat && !grad_weight && !grad_bias) return GDR_OK;
-    const size_t es = subm_esize(a->dtype);
+    const size_t es = esize(a->dtype);
     if (!grad_out || misaligned(grad_out, 15)) return invalid_arg("subm_conv_backward: grad_out NULL or unaligned");
     const hipStream_t st = (hipStream_t)stream;
     const BwdWs ws = bwd_workspace(a);

@@ -154,7 +154,7 @@ int check_merge(int64_t N, int64_t S, int64_t B, int64_t C) {
 
 int32_t promoted(int32_t a, int32_t b) { return a == b ? a : GDR_NORM_F32; }
 
-bool bad_vec(const void* ptr, int32_t dt) { return misaligned(ptr, elem_bytes(dt) - 1); }
+bool bad_vec(const void* ptr, int32_t dt) { return misaligned(ptr, esize(dt) - 1); }
 
 }  // namespace
 }  // namespace gdr
@@ -199,7 +199,7 @@ int gdr_upscale_expand_backward(const void* grad_h, int64_t grad_h_stride, int32
     if (N == 0 || (!grad_t && !grad_coord && !grad_feat)) return GDR_OK;
     if (!t || !coord || !feat || !freq) return invalid_arg("upscale_expand_backward: NULL argument");
     const int W = 6 * F + C;
-    const unsigned gmask = 2 * elem_bytes(grad_h_dtype) - 1;
+    const unsigned gmask = 2 * esize(grad_h_dtype) - 1;
     if (bad_rows(feat, feat_stride, C) || misaligned(grad_feat, 15) || bad_vec(t, t_dtype) || bad_vec(grad_t, t_dtype) ||
         bad_vec(coord, coord_dtype) || bad_vec(grad_coord, coord_dtype) || bad_vec(freq, freq_dtype) ||
         bad_vec(grad_out_x, out_x_dtype) || (grad_h && (grad_h_stride < W || grad_h_stride % 2 || misaligned(grad_h, gmask))))

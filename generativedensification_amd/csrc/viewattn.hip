@@ -45,59 +45,6 @@ struct VaP {
     float scale;
 };
 
-// CK elements from / to element index idx, a multiple of CK (of 8 for CK = 16) from a 16-byte aligned base
-template <int CK>
-__device__ __forceinline__ void loadv(const void* base, int64_t idx, int dt, float (&x)[CK]) {
-    if constexpr (CK == 4) {
-        if (dt == GDR_NORM_F32) {
-            const float4 a = *reinterpret_cast<const float4*>((const float*)base + idx);
-            x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
-        } else {
-            union { uint2 raw; uint16_t e[4]; } u;
-            u.raw = *reinterpret_cast<const uint2*>((const uint16_t*)base + idx);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x[k] = up_any(u.e[k], dt);
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < CK / 8; ++q) {
-            float y[8];
-            load8(base, idx + 8 * q, dt, y);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) x[8 * q + k] = y[k];
-        }
-    }
-}
-template <int CK>
-__device__ __forceinline__ void storev(void* base, int64_t idx, int dt, const float (&x)[CK]) {
-    if constexpr (CK == 4) {
-        if (dt == GDR_NORM_F32) {
-            *reinterpret_cast<float4*>((float*)base + idx) = make_float4(x[0], x[1], x[2], x[3]);
-        } else {
-            union { uint2 raw; uint16_t e[4]; } u;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) u.e[k] = down_any(x[k], dt);
-            *reinterpret_cast<uint2*>((uint16_t*)base + idx) = u.raw;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < CK / 8; ++q) {
-            float y[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) y[k] = x[8 * q + k];
-            store8(base, idx + 8 * q, dt, y);
-        }
-    }
-}
-
-template <int CK>
-__device__ __forceinline__ float dot(const float (&a)[CK], const float (&b)[CK]) {
-    float s = a[0] * b[0];
-#pragma unroll
-    for (int k = 1; k < CK; ++k) s = fmaf(a[k], b[k], s);
-    return s;
-}
-
 // the point and head of this lane: a point's HP lanes are adjacent and never straddle a wave
 __device__ __forceinline__ void lane_of(const VaP& p, int64_t& n, int& h) {
     const int64_t gid = (int64_t)blockIdx.x * VA_BLOCK + threadIdx.x;
@@ -110,7 +57,7 @@ template <int CK>
 __device__ __forceinline__ void hold_cond(const VaP& p, int64_t n, float (&c)[VA_HOLD][CK]) {
 #pragma unroll
     for (int v = 0; v < VA_HOLD; ++v) {
-        if (v < p.V) loadv<CK>(p.cond, n * p.cond_stride + (int64_t)v * CK, p.cond_dt, c[v]);
+        if (v < p.V) load_row<CK>(p.cond, n * p.cond_stride + (int64_t)v * CK, p.cond_dt, c[v]);
         else {
 #pragma unroll
             for (int k = 0; k < CK; ++k) c[v][k] = 0.f;
@@ -142,7 +89,7 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_fwd_kernel(const VaP p) {
     if (n >= p.N || h >= p.H) return;              // (no cross-lane traffic in the forward)
     const int V = p.V;
     float t[CK], c[VA_HOLD][CK], s[VA_HOLD], u[CK];
-    loadv<CK>(p.t, n * p.t_stride + (int64_t)h * CK, p.t_dt, t);
+    load_row<CK>(p.t, n * p.t_stride + (int64_t)h * CK, p.t_dt, t);
     hold_cond<CK>(p, n, c);
 #pragma unroll
     for (int v = 0; v < VA_HOLD; ++v) s[v] = v < V ? p.scale * dot<CK>(t, c[v]) : 0.f;
@@ -156,7 +103,7 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_fwd_kernel(const VaP p) {
             for (int k = 0; k < CK; ++k) u[k] = fmaf(s[v], c[v][k], u[k]);
         }
     }
-    storev<CK>(p.out, n * p.out_stride + (int64_t)h * CK, p.out_dt, u);
+    store_row<CK>(p.out, n * p.out_stride + (int64_t)h * CK, p.out_dt, u);
 }
 
 template <int CK>
@@ -170,8 +117,8 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_bwd_kernel(const VaP p) {
     const int V = p.V;
     float t[CK], g[CK], c[VA_HOLD][CK], s[VA_HOLD], dp[VA_HOLD], dt[CK];
     if (on) {
-        loadv<CK>(p.t, n * p.t_stride + (int64_t)h * CK, p.t_dt, t);
-        loadv<CK>(p.grad, n * p.grad_stride + (int64_t)h * CK, p.grad_dt, g);
+        load_row<CK>(p.t, n * p.t_stride + (int64_t)h * CK, p.t_dt, t);
+        load_row<CK>(p.grad, n * p.grad_stride + (int64_t)h * CK, p.grad_dt, g);
     } else {
 #pragma unroll
         for (int k = 0; k < CK; ++k) t[k] = g[k] = 0.f;
@@ -202,13 +149,13 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_bwd_kernel(const VaP p) {
                 dt[k] = fmaf(ds, c[v][k], dt[k]);
                 dc[k] = group_sum(on ? fmaf(sds, t[k], s[v] * g[k]) : 0.f, hp);
             }
-            if (h == (v & (hp - 1))) storev<CK>(p.dcond, (n * V + v) * CK, p.cond_dt, dc);
+            if (h == (v & (hp - 1))) store_row<CK>(p.dcond, (n * V + v) * CK, p.cond_dt, dc);
         }
     }
     if (on) {
 #pragma unroll
         for (int k = 0; k < CK; ++k) dt[k] *= p.scale;
-        storev<CK>(p.dt, (n * p.H + h) * CK, p.t_dt, dt);
+        store_row<CK>(p.dt, (n * p.H + h) * CK, p.t_dt, dt);
     }
 }
 
@@ -222,11 +169,11 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_fwd_many_kernel(const VaP p
     const int V = p.V;
     const int64_t cbase = n * p.cond_stride;
     float t[CK], c[CK], u[CK];
-    loadv<CK>(p.t, n * p.t_stride + (int64_t)h * CK, p.t_dt, t);
+    load_row<CK>(p.t, n * p.t_stride + (int64_t)h * CK, p.t_dt, t);
     float m = -INFINITY;
 #pragma unroll 1
     for (int v = 0; v < V; ++v) {
-        loadv<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
+        load_row<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
         m = fmaxf(m, p.scale * dot<CK>(t, c));
     }
     float l = 0.f;
@@ -234,7 +181,7 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_fwd_many_kernel(const VaP p
     for (int k = 0; k < CK; ++k) u[k] = 0.f;
 #pragma unroll 1
     for (int v = 0; v < V; ++v) {
-        loadv<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
+        load_row<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
         const float e = expf(p.scale * dot<CK>(t, c) - m);
         l += e;
 #pragma unroll
@@ -243,7 +190,7 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_fwd_many_kernel(const VaP p
     const float inv = 1.0f / l;
 #pragma unroll
     for (int k = 0; k < CK; ++k) u[k] *= inv;
-    storev<CK>(p.out, n * p.out_stride + (int64_t)h * CK, p.out_dt, u);
+    store_row<CK>(p.out, n * p.out_stride + (int64_t)h * CK, p.out_dt, u);
 }
 
 template <int CK>
@@ -258,8 +205,8 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_bwd_many_kernel(const VaP p
     const int64_t cbase = n * p.cond_stride;
     float t[CK], g[CK], c[CK], dt[CK], dc[CK];
     if (on) {
-        loadv<CK>(p.t, n * p.t_stride + (int64_t)h * CK, p.t_dt, t);
-        loadv<CK>(p.grad, n * p.grad_stride + (int64_t)h * CK, p.grad_dt, g);
+        load_row<CK>(p.t, n * p.t_stride + (int64_t)h * CK, p.t_dt, t);
+        load_row<CK>(p.grad, n * p.grad_stride + (int64_t)h * CK, p.grad_dt, g);
     } else {
 #pragma unroll
         for (int k = 0; k < CK; ++k) t[k] = g[k] = 0.f;
@@ -270,7 +217,7 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_bwd_many_kernel(const VaP p
     float m = -INFINITY, pivot = 0.f;
 #pragma unroll 1
     for (int v = 0; v < V; ++v) {
-        loadv<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
+        load_row<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
         const float s = p.scale * dot<CK>(t, c);
         if (s > m) { m = s; pivot = dot<CK>(g, c); }
     }
@@ -278,7 +225,7 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_bwd_many_kernel(const VaP p
     float l = 0.f, a = 0.f;
 #pragma unroll 1
     for (int v = 0; v < V; ++v) {
-        loadv<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
+        load_row<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
         const float e = expf(p.scale * dot<CK>(t, c) - m);
         l += e;
         a = fmaf(e, dot<CK>(g, c) - pivot, a);
@@ -288,7 +235,7 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_bwd_many_kernel(const VaP p
     for (int k = 0; k < CK; ++k) dt[k] = 0.f;
 #pragma unroll 1
     for (int v = 0; v < V; ++v) {                   // (uniform trip count: the butterflies meet whole groups)
-        loadv<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
+        load_row<CK>(p.cond, cbase + (int64_t)v * CK, p.cond_dt, c);
         const float pv = expf(p.scale * dot<CK>(t, c) - m) * inv;
         const float ds = pv * ((dot<CK>(g, c) - pivot) - mean);
         const float sds = p.scale * ds;
@@ -297,12 +244,12 @@ __global__ __launch_bounds__(VA_BLOCK) void viewattn_bwd_many_kernel(const VaP p
             dt[k] = fmaf(ds, c[k], dt[k]);
             dc[k] = group_sum(on ? fmaf(sds, t[k], pv * g[k]) : 0.f, hp);
         }
-        if (h == (v & (hp - 1))) storev<CK>(p.dcond, (n * V + v) * CK, p.cond_dt, dc);
+        if (h == (v & (hp - 1))) store_row<CK>(p.dcond, (n * V + v) * CK, p.cond_dt, dc);
     }
     if (on) {
 #pragma unroll
         for (int k = 0; k < CK; ++k) dt[k] *= p.scale;
-        storev<CK>(p.dt, (n * p.H + h) * CK, p.t_dt, dt);
+        store_row<CK>(p.dt, (n * p.H + h) * CK, p.t_dt, dt);
     }
 }
 

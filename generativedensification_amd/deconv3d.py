@@ -57,7 +57,7 @@ GRAD_WEIGHT_SLAB_ROWS = L.GDR_DECONV3D_SLAB_MIN       # the weight gradient cuts
 # reference's four lines, on purpose: the A/B of scripts/bench_deconv3d.py)
 TAIL_BACKEND = "hip"
 
-_DTYPES = M.NORM_DTYPES
+_DTYPES = M.DTYPES
 _dense = M.dense
 _NO_CPU = "the HIP transposed convolution runs on ROCm/HIP tensors only (no CPU fallback)"
 

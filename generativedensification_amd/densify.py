@@ -45,35 +45,17 @@ POINT_KEYS = ("coord", "feat", "global_feat", "offset", "grid_size", "leaf_point
 LEAF_POINT_KEYS = ("coord", "feat", "offset", "grid_size")
 MASK_RES_KEYS = ("raw_prob", "prob", "non_leaf", "non_leaf_offset", "leaf", "leaf_offset")
 
-_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-           torch.float32: L.GDR_NORM_DTYPES["f32"]}
+_DTYPES = M.DTYPES
 _NO_CPU = "the HIP densification masks run on ROCm/HIP tensors only (no CPU fallback)"
 
 
 # ---- argument checks ------------------------------------------------------------------------------------------------------
 
-def _check_float(name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor, not {type(t).__name__}")
-    if t.dtype not in _DTYPES:
-        raise TypeError(f"{name} must be float32, float16 or bfloat16, not {t.dtype}")
-
-
 def _check_vector(name, t):
     """t (N,) or (N, 1) of a floating dtype"""
-    _check_float(name, t)
+    M.check_float(name, t)
     if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] != 1):
         raise ValueError(f"{name} must be (N,) or (N, 1), got {tuple(t.shape)}")
-
-
-def _check_devices(named):
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError(_NO_CPU)
-    dev = named[0][1].device
-    for name, t in named:
-        if t.device != dev:
-            raise RuntimeError(f"{name} must live on {named[0][0]}'s device ({dev}), not {t.device}")
 
 
 def _check_offset(offset):
@@ -95,7 +77,7 @@ def _check_ratio(ratio):
 
 
 def _check_rows(name, t, N=None):
-    _check_float(name, t)
+    M.check_float(name, t)
     if t.dim() != 2:
         raise ValueError(f"{name} must have 2 dimensions, got {tuple(t.shape)}")
     if N is not None and t.shape[0] != N:
@@ -116,18 +98,6 @@ def _check_mask(mask, N):
         raise ValueError(f"mask must be ({N},), got {tuple(mask.shape)}")
 
 
-def _rows(t):
-    """t (rows, C) as the kernels read rows: unit channel stride, a 16-byte aligned base, a row stride that is a multiple of 8
-    (a copy only where the layout forces one)."""
-    if t.shape[0] and (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.shape[1] or t.data_ptr() % 16):
-        t = t.contiguous()
-    return t
-
-
-def _stride0(t):
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 8)
-
-
 # ---- selection ------------------------------------------------------------------------------------------------------------
 
 @torch.no_grad()
@@ -137,7 +107,7 @@ def _select(x, ratio, offset, mode):
     ratio = _check_ratio(ratio)
     if x.shape[0] > MAX_ROWS:
         raise ValueError("more than 2^30 rows")
-    _check_devices((("x", x), ("offset", offset)))
+    M.check_devices((("x", x), ("offset", offset)), _NO_CPU)
     N, B, dev = x.shape[0], offset.shape[0], x.device
     x, offset = x.detach().reshape(-1).contiguous(), offset.long().contiguous()
     # top-p compares with the ratio as the reference's `x_cumsum <= ratio` sees it: cast to x's dtype (a host-side cast)
@@ -181,7 +151,7 @@ def top_k(x, ratio, batch):
     if batch.dim() != 1 or batch.shape[0] != x.shape[0]:
         raise ValueError(f"batch must be ({x.shape[0]},), got {tuple(batch.shape)}")
     ratio = _check_ratio(ratio)
-    _check_devices((("x", x), ("batch", batch)))
+    M.check_devices((("x", x), ("batch", batch)), _NO_CPU)
     N, dev = x.shape[0], x.device
     if N == 0:
         return torch.empty(0, dtype=torch.bool, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
@@ -208,8 +178,8 @@ def top_p(x, ratio, offset):
 def _rows_backward(lib, mask, dest, N, Cn, g_sel, g_rest, n_sel, n_rest, feat, prob, gc_sel, gc_rest, coord_shape, coord_dtype,
                    need_feat, need_prob, need_coord, dev):
     """One launch of gdr_densify_rows_backward -> (grad_feat, grad_prob as (N,), grad_coord), None where not wanted."""
-    g_sel = _rows(g_sel)
-    stride = _stride0(g_sel)
+    g_sel = M.rows2d(g_sel)
+    stride = M.stride0(g_sel)
     if g_rest is not None:                          # (the two sides share one row stride)
         g_sel, g_rest, stride = g_sel.contiguous(), g_rest.contiguous(), Cn
     grad_feat = torch.empty(N, Cn, dtype=feat.dtype, device=dev) if need_feat else None
@@ -220,7 +190,7 @@ def _rows_backward(lib, mask, dest, N, Cn, g_sel, g_rest, n_sel, n_rest, feat, p
     if N:
         L.check(lib.gdr_densify_rows_backward(M.ptr(mask), M.ptr(dest), N, Cn, M.ptr_or_none_if_empty(g_sel),
                                               M.ptr_or_none_if_empty(g_rest), stride, _DTYPES[g_sel.dtype], n_sel, n_rest,
-                                              feat.data_ptr(), _stride0(feat), _DTYPES[feat.dtype], M.ptr(prob),
+                                              feat.data_ptr(), M.stride0(feat), _DTYPES[feat.dtype], M.ptr(prob),
                                               _DTYPES[prob.dtype] if prob is not None else 0,
                                               M.ptr_or_none_if_empty(gc_sel) if need_coord else None,
                                               M.ptr_or_none_if_empty(gc_rest) if need_coord else None, D, es, M.ptr(grad_feat),
@@ -233,11 +203,11 @@ class _SteGate(torch.autograd.Function):
     def forward(ctx, feat, prob, mask, out_dtype):
         N, Cn = feat.shape
         dev = feat.device
-        feat = _rows(feat)
+        feat = M.rows2d(feat)
         with torch.cuda.device(dev):
             out = torch.empty(N, Cn, dtype=out_dtype, device=dev)
             if N:
-                L.check(L.load().gdr_densify_gate_forward(feat.data_ptr(), _stride0(feat), _DTYPES[feat.dtype], M.ptr(mask), N, Cn,
+                L.check(L.load().gdr_densify_gate_forward(feat.data_ptr(), M.stride0(feat), _DTYPES[feat.dtype], M.ptr(mask), N, Cn,
                                                           out.data_ptr(), _DTYPES[out_dtype], M.stream()), "gdr_densify_gate_forward")
         ctx.save_for_backward(feat, prob)
         return out
@@ -269,7 +239,7 @@ def ste_gate(feat, prob, mask=None):
         _check_mask(mask, N)
         named.append(("mask", mask))
         mask = mask.contiguous()
-    _check_devices(named)
+    M.check_devices(named, _NO_CPU)
     return _SteGate.apply(feat, prob, mask, torch.promote_types(feat.dtype, prob.dtype))
 
 
@@ -278,7 +248,7 @@ class _SplitRows(torch.autograd.Function):
     def forward(ctx, mask, coord, feat, prob, n_selected):
         N, Cn = feat.shape
         dev = feat.device
-        feat, coord = _rows(feat), coord.contiguous()
+        feat, coord = M.rows2d(feat), coord.contiguous()
         out_dtype = feat.dtype if prob is None else torch.promote_types(feat.dtype, prob.dtype)
         lib = L.load()
         with torch.cuda.device(dev):
@@ -296,7 +266,7 @@ class _SplitRows(torch.autograd.Function):
             coord_sel, coord_rest = coord.new_empty(n_sel, D), coord.new_empty(n_rest, D)
             feat_sel = torch.empty(n_sel, Cn, dtype=out_dtype, device=dev)
             feat_rest = torch.empty(n_rest, Cn, dtype=out_dtype, device=dev)
-            L.check(lib.gdr_densify_split_forward(mask.data_ptr(), dest.data_ptr(), N, Cn, feat.data_ptr(), _stride0(feat),
+            L.check(lib.gdr_densify_split_forward(mask.data_ptr(), dest.data_ptr(), N, Cn, feat.data_ptr(), M.stride0(feat),
                                                   _DTYPES[feat.dtype], M.ptr_or_none_if_empty(coord), D, coord.element_size(), n_sel,
                                                   n_rest, M.ptr_or_none_if_empty(feat_sel), M.ptr_or_none_if_empty(feat_rest),
                                                   _DTYPES[out_dtype], M.ptr_or_none_if_empty(coord_sel),
@@ -348,7 +318,7 @@ def split_rows(mask, coord, feat, prob=None, n_selected=None):
         n_selected = int(n_selected)
         if not 0 <= n_selected <= N:
             raise ValueError(f"n_selected must lie in 0..{N}, got {n_selected}")
-    _check_devices(named)
+    M.check_devices(named, _NO_CPU)
     return _SplitRows.apply(mask.contiguous(), coord, feat, prob, n_selected)
 
 

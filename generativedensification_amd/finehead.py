@@ -71,7 +71,7 @@ SH_DIMS = (3, 12, 27, 48)
 # the project's rule ships "hip" only where it measured faster.  gaussian_head itself always runs the kernels.
 HEAD_BACKEND = "torch"
 
-_DTYPES = M.NORM_DTYPES
+_DTYPES = M.DTYPES
 _dense = M.dense
 _NO_CPU = "the HIP fine head runs on ROCm/HIP tensors only (no CPU fallback)"
 

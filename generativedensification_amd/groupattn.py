@@ -55,29 +55,9 @@ MAX_ROWS = (1 << 31) - 1
 # and the shape lie inside that kernel's envelope (INTEGRATION §15 has the measured recommendation per mode)
 CONV_BACKEND = "torch"
 
-_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-           torch.float32: L.GDR_NORM_DTYPES["f32"]}
-_F32 = L.GDR_NORM_DTYPES["f32"]
+_DTYPES = M.DTYPES
+_F32 = _DTYPES[torch.float32]
 _NO_CPU = "the HIP group attention runs on ROCm/HIP tensors only (no CPU fallback)"
-
-
-def _check_float(name, t, dims=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor, not {type(t).__name__}")
-    if t.dtype not in _DTYPES:
-        raise TypeError(f"{name} must be float32, float16 or bfloat16, not {t.dtype}")
-    if dims is not None and t.dim() != dims:
-        raise ValueError(f"{name} must have {dims} dimension{'s' if dims > 1 else ''}, got {tuple(t.shape)}")
-
-
-def _check_devices(named):
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError(_NO_CPU)
-    dev = named[0][1].device
-    for name, t in named:
-        if t.device != dev:
-            raise RuntimeError(f"{name} must live on {named[0][0]}'s device ({dev}), not {t.device}")
 
 
 def _dt(t):
@@ -144,7 +124,7 @@ def group_cross_attention(q, k, v, scale, num_heads):
     """q (M, Lq, E), k and v (M, Lk, E), E = num_heads * Dh -> (M, Lq, E) of q's dtype: per group m and head h,
     softmax_j(scale <q[m, i, h], k[m, j, h]>) applied to v[m, :, h]."""
     for name, t in (("q", q), ("k", k), ("v", v)):
-        _check_float(name, t, 3)
+        M.check_float(name, t, 3)
     H = int(num_heads)
     m, lq, e = q.shape
     lk = k.shape[1]
@@ -163,7 +143,7 @@ def group_cross_attention(q, k, v, scale, num_heads):
     scale = float(scale)
     if scale != scale:
         raise ValueError("scale is NaN")
-    _check_devices((("q", q), ("k", k), ("v", v)))
+    M.check_devices((("q", q), ("k", k), ("v", v)), _NO_CPU)
     return _GroupAttention.apply(q, k, v, H, scale)
 
 
@@ -180,7 +160,7 @@ def _norm_out_dtype(x, out_dtype):
 def _check_affine(weight, bias, C):
     for name, t in (("weight", weight), ("bias", bias)):
         if t is not None:
-            _check_float(name, t, 1)
+            M.check_float(name, t, 1)
             if t.shape[0] != C:
                 raise ValueError(f"{name} must have {C} elements, got {tuple(t.shape)}")
 
@@ -201,13 +181,7 @@ def _check_volume(shape, bs):
     return B * D * H * W
 
 
-def _dense(t):
-    """t as dense rows from a 16-byte aligned base (None stays None)"""
-    if t is not None and t.numel() and (not t.is_contiguous() or t.data_ptr() % 16):
-        t = t.contiguous()
-        if t.data_ptr() % 16:
-            t = t.clone()
-    return t
+_dense = M.dense_aligned
 
 
 def _affine_grads(ctx, weight, bias, which):
@@ -273,7 +247,7 @@ def patchify_layer_norm(vol, block_size, weight=None, bias=None, eps=1e-5, out_d
     """vol (B, C, D, H, W) -> (patches, normed), both (B G, bs^3, C): the rows of vol in the reference's patch order (vol's
     dtype and the same bits; rounded to patches_dtype where one is given) and F.layer_norm(patches) over C (out_dtype; by
     default float32 under autocast, else vol's dtype).  A vol that is not channels_last_3d is made so with one copy."""
-    _check_float("vol", vol)
+    M.check_float("vol", vol)
     bs = int(block_size)
     _check_volume(vol.shape, bs)
     _check_affine(weight, bias, vol.shape[1])
@@ -282,7 +256,7 @@ def patchify_layer_norm(vol, block_size, weight=None, bias=None, eps=1e-5, out_d
         patches_dtype = vol.dtype
     elif patches_dtype not in _DTYPES:
         raise TypeError(f"patches_dtype must be float32, float16 or bfloat16, not {patches_dtype}")
-    _check_devices([("vol", vol)] + [(n, t) for n, t in (("weight", weight), ("bias", bias)) if t is not None])
+    M.check_devices([("vol", vol)] + [(n, t) for n, t in (("weight", weight), ("bias", bias)) if t is not None], _NO_CPU)
     return _PatchifyLayerNorm.apply(vol, weight, bias, bs, float(eps), patches_dtype, out_dtype)
 
 
@@ -330,7 +304,7 @@ class _LayerNormUnpatchify(torch.autograd.Function):
 def layer_norm_unpatchify(patches, vol_shape, block_size, weight=None, bias=None, eps=1e-5, out_dtype=None):
     """patches (B G, bs^3, C) in patch order, vol_shape (B, C, D, H, W) -> F.layer_norm(patches) over C as a volume of that
     logical shape with channels_last_3d strides (out_dtype; by default float32 under autocast, else patches' dtype)."""
-    _check_float("patches", patches, 3)
+    M.check_float("patches", patches, 3)
     bs = int(block_size)
     shape = tuple(int(s) for s in vol_shape)
     rows = _check_volume(shape, bs)
@@ -339,7 +313,7 @@ def layer_norm_unpatchify(patches, vol_shape, block_size, weight=None, bias=None
         raise ValueError(f"a volume {shape} in blocks of {bs} has patches ({rows // bs ** 3}, {bs ** 3}, {C}), got {tuple(patches.shape)}")
     _check_affine(weight, bias, C)
     out_dtype = _norm_out_dtype(patches, out_dtype)
-    _check_devices([("patches", patches)] + [(n, t) for n, t in (("weight", weight), ("bias", bias)) if t is not None])
+    M.check_devices([("patches", patches)] + [(n, t) for n, t in (("weight", weight), ("bias", bias)) if t is not None], _NO_CPU)
     return _LayerNormUnpatchify.apply(patches, weight, bias, shape, bs, float(eps), out_dtype)
 
 

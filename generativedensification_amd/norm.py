@@ -32,31 +32,11 @@ MAX_CHANNELS, MAX_SEGMENTS = L.GDR_NORM_MAX_CHANNELS, L.GDR_NORM_MAX_SEGMENTS
 MAX_FREQS, MAX_UPSCALE = L.GDR_NORM_MAX_FREQS, L.GDR_NORM_MAX_UPSCALE
 MAX_ROWS = (1 << 31) - 1
 
-_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-           torch.float32: L.GDR_NORM_DTYPES["f32"]}
+_DTYPES = M.DTYPES
 _NO_CPU = "the HIP row normalisations run on ROCm/HIP tensors only (no CPU fallback)"
 
 
 # ---- argument checks ------------------------------------------------------------------------------------------------------
-
-def _check_float(name, t, dims):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor, not {type(t).__name__}")
-    if t.dtype not in _DTYPES:
-        raise TypeError(f"{name} must be float32, float16 or bfloat16, not {t.dtype}")
-    if t.dim() != dims:
-        raise ValueError(f"{name} must have {dims} dimension{'s' if dims > 1 else ''}, got {tuple(t.shape)}")
-
-
-def _check_devices(named):
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError(_NO_CPU)
-    dev = named[0][1].device
-    for name, t in named:
-        if t.device != dev:
-            raise RuntimeError(f"{name} must live on {named[0][0]}'s device ({dev}), not {t.device}")
-
 
 def _check_channels(C):
     if C < 8 or C > MAX_CHANNELS or C % 8:
@@ -74,18 +54,6 @@ def _result_dtype(*dtypes):
     return res
 
 
-def _rows(t):
-    """t (rows, C) as the kernels read rows: unit channel stride, a 16-byte aligned base, a row stride that is a multiple of 8
-    (a copy only where the layout forces one)."""
-    if t.shape[0] and (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.shape[1] or t.data_ptr() % 16):
-        t = t.contiguous()
-    return t
-
-
-def _stride0(t):
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 8)
-
-
 # ---- A: AdaLayerNorm ------------------------------------------------------------------------------------------------------
 
 class _AdaLayerNorm(torch.autograd.Function):
@@ -93,12 +61,12 @@ class _AdaLayerNorm(torch.autograd.Function):
     def forward(ctx, feat, scale, offset, eps, out_dtype):
         N, C = feat.shape
         B, dev = scale.shape[0], feat.device
-        feat, scale = _rows(feat), _rows(scale)
+        feat, scale = M.rows2d(feat), M.rows2d(scale)
         with torch.cuda.device(dev):
             out = torch.empty(N, C, dtype=out_dtype, device=dev)
             if N:
-                L.check(L.load().gdr_norm_ada_forward(feat.data_ptr(), _stride0(feat), _DTYPES[feat.dtype], scale.data_ptr(),
-                                                      _stride0(scale), _DTYPES[scale.dtype], offset.data_ptr(), N, B, C, eps,
+                L.check(L.load().gdr_norm_ada_forward(feat.data_ptr(), M.stride0(feat), _DTYPES[feat.dtype], scale.data_ptr(),
+                                                      M.stride0(scale), _DTYPES[scale.dtype], offset.data_ptr(), N, B, C, eps,
                                                       out.data_ptr(), _DTYPES[out_dtype], M.stream()), "gdr_norm_ada_forward")
         ctx.save_for_backward(feat, scale, offset)
         ctx.eps = eps
@@ -110,7 +78,7 @@ class _AdaLayerNorm(torch.autograd.Function):
         feat, scale, offset = ctx.saved_tensors
         N, C = feat.shape
         B, dev = scale.shape[0], feat.device
-        grad_out = _rows(grad_out)
+        grad_out = M.rows2d(grad_out)
         lib = L.load()
         with torch.cuda.device(dev):
             grad_feat = torch.empty(N, C, dtype=feat.dtype, device=dev)
@@ -119,9 +87,9 @@ class _AdaLayerNorm(torch.autograd.Function):
             if nbytes == 0:
                 L.check(-1, "gdr_norm_ada_backward_bytes")
             ws, base, usable = M.workspace(nbytes, dev)
-            L.check(lib.gdr_norm_ada_backward(M.ptr_or_none_if_empty(grad_out), _stride0(grad_out), _DTYPES[grad_out.dtype],
-                                              M.ptr_or_none_if_empty(feat), _stride0(feat), _DTYPES[feat.dtype], scale.data_ptr(),
-                                              _stride0(scale), _DTYPES[scale.dtype], offset.data_ptr(), N, B, C, ctx.eps, base,
+            L.check(lib.gdr_norm_ada_backward(M.ptr_or_none_if_empty(grad_out), M.stride0(grad_out), _DTYPES[grad_out.dtype],
+                                              M.ptr_or_none_if_empty(feat), M.stride0(feat), _DTYPES[feat.dtype], scale.data_ptr(),
+                                              M.stride0(scale), _DTYPES[scale.dtype], offset.data_ptr(), N, B, C, ctx.eps, base,
                                               usable, M.ptr_or_none_if_empty(grad_feat), grad_scale.data_ptr(), M.stream()),
                     "gdr_norm_ada_backward")
         return grad_feat, grad_scale, None, None, None
@@ -130,8 +98,8 @@ class _AdaLayerNorm(torch.autograd.Function):
 def ada_layer_norm(feat, scale, offset, eps=1e-5):
     """feat (N, C), scale (B, C), offset (B,) integer segment ends on the device -> (N, C):
     out[i] = scale[b] * layer_norm(feat[i]) for offset[b - 1] <= i < offset[b]; rows at or behind offset[-1] are zero."""
-    _check_float("feat", feat, 2)
-    _check_float("scale", scale, 2)
+    M.check_float("feat", feat, 2)
+    M.check_float("scale", scale, 2)
     if not isinstance(offset, torch.Tensor):
         raise TypeError(f"offset must be a tensor, not {type(offset).__name__}")
     if offset.dtype.is_floating_point or offset.dtype.is_complex or offset.dtype == torch.bool:
@@ -146,7 +114,7 @@ def ada_layer_norm(feat, scale, offset, eps=1e-5):
     _check_channels(C)
     if N > MAX_ROWS:
         raise ValueError("more than 2^31 - 1 rows")
-    _check_devices((("feat", feat), ("scale", scale), ("offset", offset)))
+    M.check_devices((("feat", feat), ("scale", scale), ("offset", offset)), _NO_CPU)
     return _AdaLayerNorm.apply(feat, scale, offset.long().contiguous(), float(eps), _result_dtype(feat.dtype, scale.dtype))
 
 
@@ -179,11 +147,11 @@ class _PeConcatLayerNorm(torch.autograd.Function):
         P, C = feat.shape
         F, dev = frequencies.shape[0], feat.device
         W = 6 * F + C
-        x, feat, frequencies = x.contiguous(), _rows(feat), frequencies.contiguous()
+        x, feat, frequencies = x.contiguous(), M.rows2d(feat), frequencies.contiguous()
         with torch.cuda.device(dev):
             buf = torch.empty(P * S, (W + 7) // 8 * 8, dtype=out_dtype, device=dev)
             if P:
-                L.check(L.load().gdr_norm_pe_forward(x.data_ptr(), _DTYPES[x.dtype], feat.data_ptr(), _stride0(feat),
+                L.check(L.load().gdr_norm_pe_forward(x.data_ptr(), _DTYPES[x.dtype], feat.data_ptr(), M.stride0(feat),
                                                      _DTYPES[feat.dtype], frequencies.data_ptr(), _DTYPES[frequencies.dtype], P, S,
                                                      C, F, eps, buf.data_ptr(), buf.shape[1], _DTYPES[out_dtype], M.stream()),
                         "gdr_norm_pe_forward")
@@ -206,7 +174,7 @@ class _PeConcatLayerNorm(torch.autograd.Function):
             grad_feat = torch.empty(P, C, dtype=feat.dtype, device=dev) if need_feat else None
             if P and (need_x or need_feat):
                 L.check(L.load().gdr_norm_pe_backward(grad_out.data_ptr(), grad_out.stride(0), _DTYPES[grad_out.dtype],
-                                                      x.data_ptr(), _DTYPES[x.dtype], feat.data_ptr(), _stride0(feat),
+                                                      x.data_ptr(), _DTYPES[x.dtype], feat.data_ptr(), M.stride0(feat),
                                                       _DTYPES[feat.dtype], frequencies.data_ptr(), _DTYPES[frequencies.dtype], P,
                                                       ctx.S, C, F, ctx.eps, M.ptr(grad_x), M.ptr(grad_feat), M.stream()),
                         "gdr_norm_pe_backward")
@@ -216,9 +184,9 @@ class _PeConcatLayerNorm(torch.autograd.Function):
 def pe_concat_layer_norm(x, feat, frequencies, upscale_factor, eps=1e-5):
     """x (P * S, 3), feat (P, C), frequencies (F,) on the device, S = upscale_factor -> (P * S, 6 F + C): layer_norm without
     affine of [sin(f_k x[r, j]) at 3k + j, cos(...) at 3F + 3k + j, feat[r // S]]."""
-    _check_float("x", x, 2)
-    _check_float("feat", feat, 2)
-    _check_float("frequencies", frequencies, 1)
+    M.check_float("x", x, 2)
+    M.check_float("feat", feat, 2)
+    M.check_float("frequencies", frequencies, 1)
     S = int(upscale_factor)
     F = frequencies.shape[0]
     if F == 0:
@@ -233,6 +201,6 @@ def pe_concat_layer_norm(x, feat, frequencies, upscale_factor, eps=1e-5):
         raise ValueError(f"x must be ({P} * {S}, 3) for feat {tuple(feat.shape)}, got {tuple(x.shape)}")
     if P * S > MAX_ROWS:
         raise ValueError("more than 2^31 - 1 rows")
-    _check_devices((("feat", feat), ("x", x), ("frequencies", frequencies)))
+    M.check_devices((("feat", feat), ("x", x), ("frequencies", frequencies)), _NO_CPU)
     out_dtype = _result_dtype(frequencies.dtype, x.dtype, feat.dtype)
     return _PeConcatLayerNorm.apply(x, feat, frequencies, S, float(eps), out_dtype)

@@ -30,8 +30,7 @@ __all__ = ["segment_csr", "segment_sum_csr", "segment_mean_csr", "segment_min_cs
 
 ROWS = L.GDR_SEG_ROWS     # rows per run of the kernels (the chunk R of DESIGN §17)
 
-_DTYPES = {torch.float16: L.GDR_SEG_DTYPES["f16"], torch.bfloat16: L.GDR_SEG_DTYPES["bf16"],
-           torch.float32: L.GDR_SEG_DTYPES["f32"], torch.int64: L.GDR_SEG_DTYPES["i64"]}
+_DTYPES = {**M.DTYPES, torch.int64: L.GDR_SEG_DTYPES["i64"]}
 _NO_CPU = "the HIP segment reductions run on ROCm/HIP tensors only (no CPU fallback)"
 
 

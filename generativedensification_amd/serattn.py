@@ -52,7 +52,7 @@ SERATTN_BACKEND = "hip"
 MAX_SEQLEN = L.GDR_ATTN_MAX_SEQLEN
 HEAD_DIMS = L.GDR_ATTN_HEAD_DIMS
 MAX_ROWS = (1 << 31) - 1
-_DTYPES = {torch.float16: L.GDR_ATTN_F16, torch.bfloat16: L.GDR_ATTN_BF16, torch.float32: L.GDR_ATTN_F32}
+_DTYPES = M.DTYPES
 
 
 def in_envelope(N, C, H, patch, Tp=None):

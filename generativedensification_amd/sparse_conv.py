@@ -31,8 +31,7 @@ __all__ = ["SparseConvTensor", "SubMConv3d", "SparseModule", "SubMTable", "build
 
 AUTOCAST_DTYPE = torch.float16     # what the layer computes in under autocast (None: the features' dtype, as outside autocast)
 TABLES_BUILT = 0                   # neighbour tables built by this process (tests: two layers of one indice_key build one)
-_DTYPES = {torch.float16: L.GDR_SUBM_DTYPES["f16"], torch.bfloat16: L.GDR_SUBM_DTYPES["bf16"],
-           torch.float32: L.GDR_SUBM_DTYPES["f32"]}
+_DTYPES = M.DTYPES
 
 
 def _triple(v, what):

@@ -45,7 +45,7 @@ UPSCALE_BACKEND = "hip"
 
 MAX_CHANNELS, MAX_SEGMENTS, MAX_FREQS, MAX_UPSCALE, MAX_ROWS = (_norm.MAX_CHANNELS, _norm.MAX_SEGMENTS, _norm.MAX_FREQS,
                                                               _norm.MAX_UPSCALE, _norm.MAX_ROWS)
-_DTYPES = M.NORM_DTYPES
+_DTYPES = M.DTYPES
 _rows = M.dense_aligned
 
 
@@ -111,10 +111,10 @@ def expand(t, coord, feat, frequencies, upscale_factor, grid_size, absolute_pe=F
     """t (N, 3 S) = delta_x(in_f), coord (N, 3), feat (N, C), frequencies (F,) on the device, grid_size a Python float ->
     (out_x (N S, 3), h (N S, 6 F + C)): the child coordinates and layer_norm([sin(f x), cos(f x), feat of the parent]) without
     affine, x the offset (the child coordinate with absolute_pe)."""
-    _norm._check_float("t", t, 2)
-    _norm._check_float("coord", coord, 2)
-    _norm._check_float("feat", feat, 2)
-    _norm._check_float("frequencies", frequencies, 1)
+    M.check_float("t", t, 2)
+    M.check_float("coord", coord, 2)
+    M.check_float("feat", feat, 2)
+    M.check_float("frequencies", frequencies, 1)
     if isinstance(grid_size, torch.Tensor):
         raise TypeError("grid_size must be a Python number (a tensor would have to be read back)")
     S = int(upscale_factor)
@@ -131,7 +131,7 @@ def expand(t, coord, feat, frequencies, upscale_factor, grid_size, absolute_pe=F
                          f"{tuple(t.shape)} and {tuple(coord.shape)}")
     if N * S > MAX_ROWS:
         raise ValueError("more than 2^31 - 1 rows")
-    _norm._check_devices((("feat", feat), ("t", t), ("coord", coord), ("frequencies", frequencies)))
+    M.check_devices((("feat", feat), ("t", t), ("coord", coord), ("frequencies", frequencies)), _norm._NO_CPU)
     x_dtype = torch.promote_types(coord.dtype, t.dtype)
     h_dtype = _norm._result_dtype(frequencies.dtype, x_dtype if absolute_pe else t.dtype, feat.dtype)
     if N == 0:
@@ -191,9 +191,9 @@ def merge(skip, branch, keep, scale, offset, upscale_factor, eps=1e-5):
     """skip (N, C) on the parents, branch (N S, C), keep (N S,) / (N S, 1) or None, scale (B, C), offset (B,) the parents'
     integer segment ends on the device -> (N S, C): scale[b] * layer_norm(skip[r // S] + keep[r] * branch[r]); rows at or behind
     offset[-1] * S are zero."""
-    _norm._check_float("skip", skip, 2)
-    _norm._check_float("branch", branch, 2)
-    _norm._check_float("scale", scale, 2)
+    M.check_float("skip", skip, 2)
+    M.check_float("branch", branch, 2)
+    M.check_float("scale", scale, 2)
     if keep is not None:
         if not isinstance(keep, torch.Tensor):
             raise TypeError(f"keep must be a tensor or None, not {type(keep).__name__}")
@@ -220,7 +220,7 @@ def merge(skip, branch, keep, scale, offset, upscale_factor, eps=1e-5):
     if N * S > MAX_ROWS:
         raise ValueError("more than 2^31 - 1 rows")
     named = [("skip", skip), ("branch", branch), ("scale", scale), ("offset", offset)] + ([("keep", keep)] if keep is not None else [])
-    _norm._check_devices(tuple(named))
+    M.check_devices(tuple(named), _norm._NO_CPU)
     out_dtype = _norm._result_dtype(torch.promote_types(skip.dtype, branch.dtype), scale.dtype)
     if N == 0:
         return branch.new_empty((0, C), dtype=out_dtype)

@@ -39,39 +39,19 @@ MAX_HEADS, MAX_VIEWS = 64, 16          # include/gdr.h GDR_VIEWATTN_MAX_HEADS / 
 MAX_ROWS = 1 << 27
 KEY_WIDTHS = (4, 8, 16)
 
-_DTYPES = {torch.float16: L.GDR_NORM_DTYPES["f16"], torch.bfloat16: L.GDR_NORM_DTYPES["bf16"],
-           torch.float32: L.GDR_NORM_DTYPES["f32"]}
+_DTYPES = M.DTYPES
 _NO_CPU = "the HIP view attention runs on ROCm/HIP tensors only (no CPU fallback)"
 
 
 # ---- the core -------------------------------------------------------------------------------------------------------------
 
-def _check_float(name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor, not {type(t).__name__}")
-    if t.dtype not in _DTYPES:
-        raise TypeError(f"{name} must be float32, float16 or bfloat16, not {t.dtype}")
-
-
-def _up8(c):
-    return (c + 7) // 8 * 8
-
-
+# rows of H heads of Ck = 4 are no multiple of 8 wide: copies of them get a padded stride (M.rows2d's and M.stride0's `pad`)
 def _rows(t):
-    """t (N, C) as the kernels read rows: unit channel stride, a 16-byte aligned base, a row stride that is a multiple of 8
-    and covers the row (a copy only where the layout forces one; a row that is no multiple of 8 is padded)."""
-    N, C = t.shape
-    if N and (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < C or t.data_ptr() % 16):
-        if C % 8 == 0:
-            return t.contiguous()
-        buf = torch.empty(N, _up8(C), dtype=t.dtype, device=t.device)[:, :C]
-        buf.copy_(t)
-        return buf
-    return t
+    return M.rows2d(t, pad=True)
 
 
 def _stride0(t):
-    return t.stride(0) if t.shape[0] > 1 else _up8(t.shape[1])
+    return M.stride0(t, pad=True)
 
 
 class _ViewAttention(torch.autograd.Function):
@@ -80,7 +60,7 @@ class _ViewAttention(torch.autograd.Function):
         N, dev = t.shape[0], t.device
         t, cond = _rows(t), _rows(cond)
         with torch.cuda.device(dev):
-            out = torch.empty(N, _up8(H * Ck), dtype=t.dtype, device=dev)[:, :H * Ck]
+            out = torch.empty(N, M.up8(H * Ck), dtype=t.dtype, device=dev)[:, :H * Ck]
             if N:
                 L.check(L.load().gdr_viewattn_forward(t.data_ptr(), _stride0(t), _DTYPES[t.dtype], cond.data_ptr(), _stride0(cond),
                                                       _DTYPES[cond.dtype], N, H, Ck, V, scale, out.data_ptr(), _stride0(out),
@@ -112,8 +92,8 @@ class _ViewAttention(torch.autograd.Function):
 def view_attention_pool(t, cond, scale, num_heads=None):
     """t (N, H, Ck), or (N, H * Ck) with `num_heads=H`; cond (N, V, Ck) -> u (N, H, Ck) of t's dtype:
     u[n, h] = sum_v softmax_v(scale * <t[n, h], cond[n, v]>) * cond[n, v]."""
-    _check_float("t", t)
-    _check_float("cond", cond)
+    M.check_float("t", t)
+    M.check_float("cond", cond)
     if cond.dim() != 3:
         raise ValueError(f"cond must be (N, V, Ck), got {tuple(cond.shape)}")
     N, V, Ck = cond.shape

@@ -60,30 +60,11 @@ MAX_ROWS = (1 << 31) - 1
 # purpose: the A/B of scripts/bench_volcond.py)
 COND_BACKEND = "hip"
 
-_DTYPES = M.NORM_DTYPES
+_DTYPES = M.DTYPES
 _NO_CPU = "the HIP volume conditioning runs on ROCm/HIP tensors only (no CPU fallback)"
 
 
 # ---- argument checks ------------------------------------------------------------------------------------------------------
-
-def _check_float(name, t, dims=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a tensor, not {type(t).__name__}")
-    if t.dtype not in _DTYPES:
-        raise TypeError(f"{name} must be float32, float16 or bfloat16, not {t.dtype}")
-    if dims is not None and t.dim() != dims:
-        raise ValueError(f"{name} must have {dims} dimension{'s' if dims > 1 else ''}, got {tuple(t.shape)}")
-
-
-def _check_devices(named):
-    for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError(_NO_CPU)
-    dev = named[0][1].device
-    for name, t in named:
-        if t.device != dev:
-            raise RuntimeError(f"{name} must live on {named[0][0]}'s device ({dev}), not {t.device}")
-
 
 def _result_dtype(*dtypes):
     """What the torch composition returns: float32 under autocast (layer_norm runs in float32 there and the products with it
@@ -94,18 +75,6 @@ def _result_dtype(*dtypes):
     for d in dtypes[1:]:
         res = torch.promote_types(res, d)
     return res
-
-
-def _rows(t):
-    """t (rows, W) as the kernels read rows: unit channel stride, a 16-byte aligned base, a row stride that is a multiple of 8
-    and covers the row (a copy only where the layout forces one)."""
-    if t.shape[0] and (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.shape[1] or t.data_ptr() % 16):
-        t = t.contiguous()
-    return t
-
-
-def _stride0(t):
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 8)
 
 
 def _row_view(x):
@@ -138,13 +107,13 @@ def _row_view(x):
 def ray_sh(rays, silu=False):
     """rays (..., 6) = (origin, direction) -> (..., 32) float32: the degree <= 3 real spherical harmonics of the unit direction
     and of the moment origin x direction; SiLU of them with silu=True.  One launch, no gradient."""
-    _check_float("rays", rays)
+    M.check_float("rays", rays)
     if rays.dim() < 1 or rays.shape[-1] != 6:
         raise ValueError(f"rays must be (..., 6), got {tuple(rays.shape)}")
     n = rays.numel() // 6
     if n * 32 > MAX_ROWS:
         raise ValueError("more than 2^31 - 1 output elements")
-    _check_devices((("rays", rays),))
+    M.check_devices((("rays", rays),), _NO_CPU)
     rays = M.dense(rays.detach())
     with torch.cuda.device(rays.device):
         out = torch.empty(*rays.shape[:-1], 32, dtype=torch.float32, device=rays.device)
@@ -166,11 +135,11 @@ class _ModLayerNorm(torch.autograd.Function):
         dev, Cn = x.device, x.shape[-1]
         xv, xs, inner, outer = _row_view(x)
         R = x.numel() // Cn
-        ss, w, b = _rows(ss), M.dense_aligned(weight) if weight is not None else None, M.dense_aligned(bias) if bias is not None else None
+        ss, w, b = M.rows2d(ss), M.dense_aligned(weight), M.dense_aligned(bias)
         with torch.cuda.device(dev):
             out = torch.empty(x.shape, dtype=out_dtype, device=dev)
             if R:
-                L.check(L.load().gdr_volcond_modln_forward(xv.data_ptr(), xs, inner, outer, _DTYPES[x.dtype], ss.data_ptr(), _stride0(ss),
+                L.check(L.load().gdr_volcond_modln_forward(xv.data_ptr(), xs, inner, outer, _DTYPES[x.dtype], ss.data_ptr(), M.stride0(ss),
                                                            _DTYPES[ss.dtype], M.ptr(w), _dt(w), M.ptr(b), _dt(b), R, Cn, eps,
                                                            out.data_ptr(), _DTYPES[out_dtype], M.stream()), "gdr_volcond_modln_forward")
         ctx.save_for_backward(xv, ss, w, b)
@@ -187,7 +156,7 @@ class _ModLayerNorm(torch.autograd.Function):
         need_x, need_ss = ctx.needs_input_grad[:2]
         need_w = ctx.meta[0] is not None and ctx.needs_input_grad[2]
         need_b = ctx.meta[1] is not None and ctx.needs_input_grad[3]
-        g = _rows(grad_out.reshape(R, Cn))
+        g = M.rows2d(grad_out.reshape(R, Cn))
         lib = L.load()
         with torch.cuda.device(dev):
             grad_x = torch.empty(shape, dtype=xv.dtype, device=dev) if need_x else None
@@ -199,8 +168,8 @@ class _ModLayerNorm(torch.autograd.Function):
             if need_w or need_b:
                 ws, base, usable = M.queried_workspace(lib.gdr_volcond_modln_backward_bytes, "gdr_volcond_modln_backward_bytes", dev, R, Cn)
             if need_x or need_ss or need_w or need_b:
-                L.check(lib.gdr_volcond_modln_backward(M.ptr_or_none_if_empty(g), _stride0(g), _DTYPES[g.dtype], M.ptr_or_none_if_empty(xv),
-                                                       xs, inner, outer, _DTYPES[xv.dtype], M.ptr_or_none_if_empty(ss), _stride0(ss),
+                L.check(lib.gdr_volcond_modln_backward(M.ptr_or_none_if_empty(g), M.stride0(g), _DTYPES[g.dtype], M.ptr_or_none_if_empty(xv),
+                                                       xs, inner, outer, _DTYPES[xv.dtype], M.ptr_or_none_if_empty(ss), M.stride0(ss),
                                                        _DTYPES[ss.dtype], M.ptr(w), _dt(w), M.ptr(b), _dt(b), R, Cn, eps, base, usable,
                                                        M.ptr_or_none_if_empty(grad_x), M.ptr_or_none_if_empty(grad_ss), M.ptr(grad_w),
                                                        M.ptr(grad_b), M.stream()), "gdr_volcond_modln_backward")
@@ -210,8 +179,8 @@ class _ModLayerNorm(torch.autograd.Function):
 def mod_layer_norm(x, shift_scale, weight=None, bias=None, eps=1e-5):
     """x (..., C) with R rows, shift_scale (R, 2C) with shift in [:, :C] and scale in [:, C:] (or (..., 2C) over the same leading
     axes), weight / bias (C,) or None -> (layer_norm(x) * weight + bias) * (1 + scale) + shift, shaped like x."""
-    _check_float("x", x)
-    _check_float("shift_scale", shift_scale)
+    M.check_float("x", x)
+    M.check_float("shift_scale", shift_scale)
     if x.dim() < 2:
         raise ValueError(f"x must be (..., C) rows with at least 2 dimensions, got {tuple(x.shape)}")
     Cn = x.shape[-1]
@@ -219,7 +188,7 @@ def mod_layer_norm(x, shift_scale, weight=None, bias=None, eps=1e-5):
     named = [("x", x), ("shift_scale", shift_scale)]
     for name, t in (("weight", weight), ("bias", bias)):
         if t is not None:
-            _check_float(name, t, 1)
+            M.check_float(name, t, 1)
             if t.shape[0] != Cn:
                 raise ValueError(f"{name} must have {Cn} elements, got {tuple(t.shape)}")
             named.append((name, t))
@@ -233,7 +202,7 @@ def mod_layer_norm(x, shift_scale, weight=None, bias=None, eps=1e-5):
         raise ValueError(f"eps must be >= 0, got {eps}")
     if R > MAX_ROWS:
         raise ValueError("more than 2^31 - 1 rows")
-    _check_devices(named)
+    M.check_devices(named, _NO_CPU)
     out_dtype = _result_dtype(*(t.dtype for _, t in named))
     if shift_scale.dim() != 2:
         shift_scale = shift_scale.reshape(R, 2 * Cn)
@@ -248,7 +217,7 @@ class _SampleTokens(torch.autograd.Function):
         dev = rows.device
         a = L.GdrVolcondSampleArgs(*args)
         rows = M.dense_aligned(rows)
-        ve2 = None if ve is None else _rows(ve[0, :a.V, :, 0, 0, 0])
+        ve2 = None if ve is None else M.rows2d(ve[0, :a.V, :, 0, 0, 0])
         bs = a.r // a.n_group
         entries = 4 * a.B * a.V * a.r ** 3
         need = any(ctx.needs_input_grad[:1])
@@ -257,7 +226,7 @@ class _SampleTokens(torch.autograd.Function):
             keys = torch.empty(entries, dtype=torch.int64, device=dev) if need else None
             wts = torch.empty(entries, dtype=torch.float32, device=dev) if need else None
             L.check(L.load().gdr_volcond_sample_forward(C.byref(a), rows.data_ptr(), _DTYPES[rows.dtype], points.data_ptr(), w2cs.data_ptr(),
-                                                        ixts.data_ptr(), M.ptr(ve2), 0 if ve2 is None else _stride0(ve2), _dt(ve2),
+                                                        ixts.data_ptr(), M.ptr(ve2), 0 if ve2 is None else M.stride0(ve2), _dt(ve2),
                                                         cond.data_ptr(), _DTYPES[out_dtype], M.ptr(keys), M.ptr(wts), M.stream()),
                     "gdr_volcond_sample_forward")
         ctx.save_for_backward(keys, wts)
@@ -317,7 +286,7 @@ def sample_tokens(rows, points, w2cs, ixts, img_hw, n_group, view_embed=None, ou
     """rows (B V, h, w, C), points (r^3, 3) in (d, h, w) grid order, w2cs (B V, 4, 4), ixts (B V, 3, 3) of an img_hw = (H, W)
     image, view_embed (1, >= V, E, 1, 1, 1) or None -> cond (B g^3, V bs^3, C + E), g = n_group, bs = r / g.  n_views = V (default:
     every camera is a view of one batch element)."""
-    _check_float("rows", rows, 4)
+    M.check_float("rows", rows, 4)
     BV, h, w, Cn = rows.shape
     if isinstance(n_group, bool) or not isinstance(n_group, int) or n_group < 1:
         raise ValueError(f"n_group must be a positive integer, got {n_group!r}")
@@ -341,7 +310,7 @@ def sample_tokens(rows, points, w2cs, ixts, img_hw, n_group, view_embed=None, ou
         raise ValueError(f"n_group {n_group} does not divide the grid resolution {r}")
     E = 0
     if view_embed is not None:
-        _check_float("view_embed", view_embed)
+        M.check_float("view_embed", view_embed)
         if view_embed.dim() != 6 or view_embed.shape[0] != 1 or view_embed.shape[3:] != (1, 1, 1) or view_embed.shape[1] < V:
             raise ValueError(f"view_embed must be (1, >= {V}, E, 1, 1, 1), got {tuple(view_embed.shape)}")
         E = view_embed.shape[2]

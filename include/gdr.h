@@ -52,6 +52,12 @@ extern "C" {
 #define GDR_ERR_UNSUPPORTED (-3)  /* sh_degree > 3, image too large for the key layout */
 #define GDR_ERR_WORKSPACE (-4)    /* caller workspace smaller than required            */
 
+/* The storage type of a buffer's elements, wherever an entry point takes a `dtype`.  Each module's own names below
+ * (GDR_ATTN_*, GDR_SUBM_*, GDR_SEG_*, GDR_NORM_*) are these; which of them an entry point accepts is stated with it. */
+#define GDR_F16 0
+#define GDR_BF16 1
+#define GDR_F32 2
+
 /* Size limits of this build (checked at every entry point, GDR_ERR_UNSUPPORTED beyond them):
  * per-Gaussian element offsets are computed in 32-bit registers up to 9*N (SH rows use 64-bit
  * offsets), and num_rendered is a 32-bit counter as in the reference's int num_rendered. */
@@ -649,8 +655,8 @@ int gdr_tsdf_clusters(int32_t F, const int64_t* keys, const int64_t* tri_of, int
  * sequence longer than max_seqlen is cut (its further rows are not written).  One launch each, no atomics: two runs are
  * bitwise equal.  No host synchronisation. */
 #define GDR_ATTN_MAX_SEQLEN 256
-#define GDR_ATTN_F16 0
-#define GDR_ATTN_BF16 1
+#define GDR_ATTN_F16 GDR_F16
+#define GDR_ATTN_BF16 GDR_BF16
 typedef struct gdr_attn_args {
     int32_t total, batch, H, D;
     int32_t max_seqlen, fixed_len;   /* fixed_len: used only when cu_seqlens == NULL */
@@ -684,7 +690,7 @@ int gdr_attn_backward(const gdr_attn_args* a, const void* dout, const int64_t* d
  * order / inverse outside [0, N) / [0, Tp) are skipped and cu_seqlens is clamped to [0, Tp].
  * Envelope: D in {8, 16, 32, 64}, H >= 1, 1 <= max_seqlen <= GDR_ATTN_MAX_SEQLEN, N and Tp >= 0; N == 0 or Tp == 0 is a
  * no-op.  One launch each, no atomics, no scratch, no host synchronisation. */
-#define GDR_ATTN_F32 2     /* the gather entry points only */
+#define GDR_ATTN_F32 GDR_F32     /* the gather entry points only */
 typedef struct gdr_attn_gather_args {
     int32_t N, Tp, batch, H, D;
     int32_t max_seqlen;              /* the patch size: no sequence is longer */
@@ -804,9 +810,9 @@ int gdr_sample_views_backward(const gdr_pointfeat_args* a, const float* grad_out
  *   representatives and zero rows for the rest, grad_weight[k] = sum_r feat[nbr[k, r]]^T @ G[r], grad_bias = column sums of
  *   grad_out.  workspace: gdr_subm_backward_bytes(a), 256-byte aligned.  No atomics: two runs are bitwise equal.
  * Envelope: Cin, Cout multiples of 8 in 8..GDR_SUBM_MAX_CHANNELS, 0 <= N <= GDR_SUBM_MAX_POINTS (the sort's limit). */
-#define GDR_SUBM_F16 0
-#define GDR_SUBM_BF16 1
-#define GDR_SUBM_F32 2
+#define GDR_SUBM_F16 GDR_F16
+#define GDR_SUBM_BF16 GDR_BF16
+#define GDR_SUBM_F32 GDR_F32
 #define GDR_SUBM_MAX_TAPS 125
 #define GDR_SUBM_MAX_CHANNELS 512
 #define GDR_SUBM_MAX_POINTS (1 << 30)
@@ -846,9 +852,9 @@ int gdr_subm_conv_backward(const gdr_subm_args* a, const void* grad_out, const v
  *   written); the index must be non-decreasing in that order.  1 launch. */
 #define GDR_SEG_ROWS 32                /* rows per run of the reduce and the gather */
 #define GDR_SEG_MAX_CHANNELS 65536
-#define GDR_SEG_F16 0
-#define GDR_SEG_BF16 1
-#define GDR_SEG_F32 2
+#define GDR_SEG_F16 GDR_F16
+#define GDR_SEG_BF16 GDR_BF16
+#define GDR_SEG_F32 GDR_F32
 #define GDR_SEG_I64 3
 #define GDR_SEG_SUM 0
 #define GDR_SEG_MEAN 1
@@ -885,9 +891,9 @@ int gdr_seg_ptr_from_sorted(const int64_t* index, const int64_t* perm, int64_t N
  * pe_backward: grad_out (P * S, 6 F + C) through grad_stride, which must be even, from a base aligned to two elements (a
  *   16-byte base and a stride that is a multiple of 8 take the wide path).  grad_x (P * S, 3) dense of x_dtype, grad_feat
  *   (P, C) dense of feat_dtype, 16-byte aligned; a NULL output is not wanted.  1 launch. */
-#define GDR_NORM_F16 0
-#define GDR_NORM_BF16 1
-#define GDR_NORM_F32 2
+#define GDR_NORM_F16 GDR_F16
+#define GDR_NORM_BF16 GDR_BF16
+#define GDR_NORM_F32 GDR_F32
 #define GDR_NORM_ROWS 32               /* rows per workgroup of the ada backward: one dscale partial pair per that many rows */
 #define GDR_NORM_MAX_CHANNELS 1024
 #define GDR_NORM_MAX_SEGMENTS 1024

@@ -196,7 +196,9 @@ def test_entry_points_are_declared():
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     names = [f.strip() for decl in body.split(";") if decl.strip() for f in decl.strip().split(" ", 1)[1].split(",")]
     assert names == [f[0] for f in L.GdrAttnGatherArgs._fields_] and ctypes.sizeof(L.GdrAttnGatherArgs) == 40
-    assert (L.GDR_ATTN_F16, L.GDR_ATTN_BF16, L.GDR_ATTN_F32) == (0, 1, 2) and re.search(r"#define GDR_ATTN_F32\s+2\b", header)
+    # GDR_ATTN_F32 is the header's GDR_F32, and that is 2
+    assert (L.GDR_ATTN_F16, L.GDR_ATTN_BF16, L.GDR_ATTN_F32) == (0, 1, 2)
+    assert re.search(r"#define GDR_ATTN_F32\s+GDR_F32\b", header) and re.search(r"#define GDR_F32\s+2\b", header)
 
 
 def test_covers_and_in_envelope():
