@@ -88,6 +88,15 @@ class GdrViewOpts(C.Structure):
                 ("global_sort", C.c_int32), ("radix_partition", C.c_int32), ("no_hints", C.c_int32)]
 
 
+class GdrBlockNorm(C.Structure):
+    """include/gdr.h GdrBlockNorm: one norm of a Block junction (csrc/block.hip)"""
+    _fields_ = [("kind", C.c_int32), ("w_dtype", C.c_int32), ("b_dtype", C.c_int32), ("eps", C.c_float), ("w", C.c_void_p),
+                ("b", C.c_void_p), ("w_stride", C.c_int64), ("grad_w", C.c_void_p), ("grad_b", C.c_void_p)]
+
+
+GDR_BLOCK_NORM_NONE, GDR_BLOCK_NORM_LN, GDR_BLOCK_NORM_LN_AFFINE, GDR_BLOCK_NORM_ADA = 0, 1, 2, 3
+
+
 class GdrSameAs(C.Structure):
     _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("a", C.c_void_p * GDR_SAME_AS_MAX),
                 ("b", C.c_void_p * GDR_SAME_AS_MAX), ("n_bytes", C.c_uint64 * GDR_SAME_AS_MAX)]
@@ -404,6 +413,13 @@ _PROTOS = {
     "gdr_upscale_merge_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                              C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                              C.c_void_p, C.c_size_t] + [C.c_void_p] * 4),
+    "gdr_block_junction_forward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 2 + [C.c_void_p, C.c_int32, C.POINTER(GdrBlockNorm),
+                                             C.POINTER(GdrBlockNorm), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gdr_block_junction_backward_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gdr_block_junction_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.POINTER(GdrBlockNorm),
+                                              C.POINTER(GdrBlockNorm), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdr_densify_select_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "gdr_densify_select": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -954,6 +954,51 @@ int gdr_upscale_merge_backward(const void* grad_out, int64_t grad_stride, int32_
                                int64_t N, int32_t S, int32_t B, int32_t C, float eps, void* workspace, size_t workspace_bytes,
                                void* grad_skip, void* grad_branch, void* grad_scale, void* stream);
 
+/* ---- the residual junctions of the point decoder's Block (csrc/block.hip; backward-compatible additions to v17) ---------------
+ * One launch for what lies between a Block's conv / attention / MLP and the next Linear: a norm of the branch, the drop-path
+ * product, the residual sum, the next norm.  The arithmetic is restated in the header of csrc/block.hip; statistics, mapping
+ * and ada's segment rules and fold are norm.hip's (one source).  The caller owns every buffer; all are device memory.  Every
+ * `*_dtype` is one of GDR_NORM_F16 / BF16 / F32 and the types of one call are independent; the arithmetic is f32.  Refusals
+ * happen before any launch; N = 0 launches no row kernel; no entry point allocates or synchronises with the host.  No atomics:
+ * two runs are bitwise equal.  Envelope: norm's (C, B, N below 2^31).  "Rows" as above.
+ *
+ * GdrBlockNorm describes one norm (NULL = GDR_BLOCK_NORM_NONE).  LN: no parameters.  LN_AFFINE: w = weight (C) or NULL (ones),
+ *   b = bias (C) or NULL (zeros), 16-byte aligned.  ADA: w = rows of scale (B, C) through w_stride, and `offset` (B int64
+ *   inclusive segment ends, clamped to [0, N] where read) is required.  grad_w / grad_b are read by the backward only: dense
+ *   outputs of w's / b's shape and dtype, written whole; NULL = not wanted and not stored.
+ * junction_forward: rows of skip and branch (N, C); keep: N values or NULL (ones); b0 = pre(branch) rounded to pre_out_dtype,
+ *   keep * b0 rounded to kept_dtype, y = skip + that rounded to y_dtype; y (N, C) dense, 16-byte aligned, every row written;
+ *   n = post(y) (N, C) dense of n_dtype, ignored when post is none.  1 launch.
+ * junction_backward: grad_y / grad_n: rows of (N, C), or NULL (zeros); grad_skip (N, C) of skip_dtype, grad_branch (N, C) of
+ *   branch_dtype, dense, 16-byte aligned, written whole; NULL = not wanted and not stored.  workspace:
+ *   gdr_block_junction_backward_bytes(N, B, C) bytes, 256-byte aligned.  1 launch + one fold per norm whose parameter
+ *   gradient is wanted. */
+#define GDR_BLOCK_NORM_NONE 0
+#define GDR_BLOCK_NORM_LN 1
+#define GDR_BLOCK_NORM_LN_AFFINE 2
+#define GDR_BLOCK_NORM_ADA 3
+typedef struct GdrBlockNorm {
+    int32_t kind;          /* GDR_BLOCK_NORM_* */
+    int32_t w_dtype, b_dtype;
+    float eps;
+    const void* w;
+    const void* b;
+    int64_t w_stride;
+    void* grad_w;
+    void* grad_b;
+} GdrBlockNorm;
+int gdr_block_junction_forward(const void* skip, int64_t skip_stride, int32_t skip_dtype, const void* branch, int64_t branch_stride,
+                               int32_t branch_dtype, const void* keep, int32_t keep_dtype, const GdrBlockNorm* pre,
+                               const GdrBlockNorm* post, const int64_t* offset, int64_t N, int32_t B, int32_t C, int32_t pre_out_dtype,
+                               int32_t kept_dtype, void* y, int32_t y_dtype, void* n, int32_t n_dtype, void* stream);
+size_t gdr_block_junction_backward_bytes(int64_t N, int32_t B, int32_t C);   /* 0: the arguments are refused */
+int gdr_block_junction_backward(const void* grad_y, int64_t grad_y_stride, int32_t grad_y_dtype, const void* grad_n,
+                                int64_t grad_n_stride, int32_t grad_n_dtype, const void* skip, int64_t skip_stride, int32_t skip_dtype,
+                                const void* branch, int64_t branch_stride, int32_t branch_dtype, const void* keep, int32_t keep_dtype,
+                                const GdrBlockNorm* pre, const GdrBlockNorm* post, const int64_t* offset, int64_t N, int32_t B, int32_t C,
+                                int32_t pre_out_dtype, int32_t kept_dtype, int32_t y_dtype, void* workspace, size_t workspace_bytes,
+                                void* grad_skip, void* grad_branch, void* stream);
+
 /* ---- densification masks of the point decoder (csrc/densify.hip; added in v17, backward-compatible) ------------------------
  * What the reference's MaskModule / MaskResModule do around their scores: per-segment top-k / top-p selection, the
  * straight-through gate and the split into selected and remaining rows.  The rules are restated in the header of
