@@ -146,12 +146,25 @@ def reference_res_module_forward(self, point):
     return point
 
 
-def reference_assemble(levels, coarse, shs_fine, mask, selected, sh_dim, opacity_shift, scaling_shift):
-    """`_union_gaussians` (the concatenation by group with its stable sort, for one sample) and the five concatenations behind it,
-    written from the recorded surface: the lines the GPU tests compare against, bit for bit"""
+ASSEMBLE_MUTANTS = ("levels_not_sorted_by_batch", "shifts_swapped")
+
+
+def reference_assemble(levels, coarse, shs_fine, mask, selected, sh_dim, opacity_shift, scaling_shift, offsets=None, mut=None):
+    """`_union_gaussians` (the concatenation by group with its stable sort) and the five concatenations behind it, written from
+    the recorded surface: the lines the GPU tests compare against, bit for bit.  offsets: per level the segment ends of its rows
+    (None: one sample).  `mut` switches one deliberate mistake on."""
     import torch
 
-    index, perm = torch.cat([torch.zeros(c.shape[0], dtype=torch.long, device=c.device) for c, _ in levels]).sort(stable=True)
+    assert mut in (None,) + ASSEMBLE_MUTANTS
+    if offsets is None:
+        batches = [torch.zeros(c.shape[0], dtype=torch.long, device=c.device) for c, _ in levels]
+    else:
+        batches = [torch.searchsorted(o, torch.arange(c.shape[0], device=c.device), right=True) for (c, _), o in zip(levels, offsets)]
+    index, perm = torch.cat(batches).sort(stable=True)
+    if mut == "levels_not_sorted_by_batch":
+        perm = torch.arange(perm.shape[0], device=perm.device)
+    if mut == "shifts_swapped":
+        opacity_shift, scaling_shift = scaling_shift, opacity_shift
     xyz = torch.cat([c for c, _ in levels], 0)[perm]
     attribute = torch.cat([a for _, a in levels], 0)[perm]
     sh, opacity, scaling, rotation = torch.split(attribute, [sh_dim, 1, 3, 4], dim=-1)

@@ -14,6 +14,7 @@ The packages they import are stood in for as make_network_record.py does:
     pytorch_lightning  LightningModule = torch.nn.Module
     timm, torch_geometric, point_prompt_training, utils.serialization   names only: nothing a Block runs reaches them (drop_path
                        is 0.0, so the Block holds an nn.Identity and no DropPath is built)
+`load_reference(stand_ins)` serves make_pointdec_record.py, which needs more of autoencoder.py; without the argument it is as above.
 flash_attn is absent, and the Block is built with enable_flash=False, upcast_attention=False, upcast_softmax=False: the
 reference's own torch attention over the same padded patches, which is the flash kernel's result in exact arithmetic (with the
 upcasts on, `.float()` would take float64 down to float32).  Nothing of the reference is copied: a file holds arrays, names,
@@ -111,7 +112,12 @@ class _GatherCsr(torch.autograd.Function):
         return torch.from_numpy(SCR.gather_csr_grad(grad_out.numpy(), ctx.indptr)), None
 
 
-def load_reference():
+def load_reference(stand_ins=None):
+    """stand_ins: None for what a Block needs (above); make_pointdec_record.py passes {"Dict", "gather_csr", "segment_csr",
+    "cumsum", "scatter", "softmax"} for the rest of autoencoder.py, and utils/serialization is then the reference's own package"""
+    full = stand_ins is not None
+    stand_ins = stand_ins or {}
+
     def stub(name, **attrs):
         m = types.ModuleType(name)
         m.__dict__.update(attrs)
@@ -123,30 +129,35 @@ def load_reference():
         def __init__(self, *a, **k):
             raise AssertionError("a stand-in for a class no Block uses was built")
 
-    def by_path(name, *parts):
-        spec = importlib.util.spec_from_file_location(name, os.path.join(REF, "lightning", "point_decoder", *parts))
+    def by_path(name, *parts, package=False):
+        path = os.path.join(REF, "lightning", "point_decoder", *parts)
+        spec = importlib.util.spec_from_file_location(name, path, submodule_search_locations=[os.path.dirname(path)] if package else None)
         mod = importlib.util.module_from_spec(spec)
         sys.modules[name] = mod
         spec.loader.exec_module(mod)
         return mod
 
     assert "flash_attn" not in sys.modules and importlib.util.find_spec("flash_attn") is None
-    stub("addict", Dict=Dict)
+    stub("addict", Dict=stand_ins.get("Dict", Dict))
     stub("pytorch_lightning", LightningModule=torch.nn.Module)
     sp = stub("spconv.pytorch", SubMConv3d=SubMConv3d, SparseConvTensor=SparseConvTensor,
               modules=types.SimpleNamespace(is_spconv_module=lambda m: isinstance(m, SubMConv3d)))
     stub("spconv", pytorch=sp)
-    stub("torch_scatter", gather_csr=lambda src, indptr: _GatherCsr.apply(src, indptr), segment_csr=None)
+    stub("torch_scatter", gather_csr=stand_ins.get("gather_csr", lambda src, indptr: _GatherCsr.apply(src, indptr)),
+         segment_csr=stand_ins.get("segment_csr"))
     stub("timm")
     stub("timm.models")
     stub("timm.models.layers", DropPath=_Any)
     stub("torch_geometric")
-    stub("torch_geometric.utils", cumsum=None, scatter=None, softmax=None)
+    stub("torch_geometric.utils", cumsum=stand_ins.get("cumsum"), scatter=stand_ins.get("scatter"), softmax=stand_ins.get("softmax"))
     pd = "lightning.point_decoder"
     for pkg in ("lightning", pd, pd + ".utils", pd + ".layers"):
         stub(pkg)
     stub(pd + ".point_prompt_training", PDNorm=_Any)
-    stub(pd + ".utils.serialization", encode=None, decode=None)
+    if full:
+        by_path(pd + ".utils.serialization", "utils", "serialization", "__init__.py", package=True)
+    else:
+        stub(pd + ".utils.serialization", encode=None, decode=None)
     by_path(pd + ".utils.misc", "utils", "misc.py")
     by_path(pd + ".utils.structure", "utils", "structure.py")
     by_path(pd + ".layers.normalization", "layers", "normalization.py")

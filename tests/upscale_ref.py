@@ -130,14 +130,17 @@ class Point(dict):
 
 
 def make_module(in_channels, out_channels, upscale_factor, n_frequencies, global_channels=24, drop_path=0.0, absolute_pe=False,
-                residual_attribute=False, is_first=True, seed=0, ada_forward=None):
+                residual_attribute=False, is_first=True, seed=0, ada_forward=None, norm="ada"):
     """A module that has what upscale.upscale_module_forward reads and nothing else of the reference: in_norm / out_norm are
     one-element containers round a LayerNorm without affine that has an `affine` Linear child, called on the point; drop_path
     draws as timm's DropPath does.  `ada_forward(self, feat, global_feat, offset)` is bound onto the norm class (the fused
     AdaLayerNorm on the GPU); the default is the torch composition, which also runs in float64 on the CPU.  Parameters come
-    from a seeded numpy draw."""
+    from a seeded numpy draw.  norm: "ada", or "ln" for the nn.LayerNorm without affine and without a child that Network
+    builds (the container hands it the features alone, as the reference's PointSequential does)."""
     import torch
     from torch import nn
+
+    assert norm in ("ada", "ln")
 
     class AdaNorm(nn.LayerNorm):
         def __init__(self, channels):
@@ -159,8 +162,11 @@ def make_module(in_channels, out_channels, upscale_factor, n_frequencies, global
 
         def forward(self, point):
             for m in self._modules.values():
-                point.feat = m(point.feat, point.global_feat, point.offset)
+                point.feat = m(point.feat, point.global_feat, point.offset) if isinstance(m, AdaNorm) else m(point.feat)
             return point
+
+    def norm_layer(channels):
+        return AdaNorm(channels) if norm == "ada" else nn.LayerNorm(channels, elementwise_affine=False)
 
     class DropPath(nn.Module):
         def __init__(self, drop_prob, scale_by_keep=True):
@@ -183,12 +189,12 @@ def make_module(in_channels, out_channels, upscale_factor, n_frequencies, global
             self.is_first, self.in_channels, self.out_channels, self.upscale_factor, self.n_frequencies = is_first, c, co, s, f
             self.enable_absolute_pe, self.enable_residual_attribute = absolute_pe, residual_attribute
             self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
-            self.in_norm = PointSeq(AdaNorm(c))
+            self.in_norm = PointSeq(norm_layer(c))
             self.delta_x = nn.Sequential(nn.Linear(c, c), nn.GELU(), nn.Linear(c, 3 * s))
             self.skip = nn.Linear(c, co)
             self.delta_f = nn.Sequential(nn.LayerNorm(c + 6 * f, elementwise_affine=False), nn.Linear(c + 6 * f, c), nn.GELU(),
                                          nn.Linear(c, co))
-            self.out_norm = PointSeq(AdaNorm(co))
+            self.out_norm = PointSeq(norm_layer(co))
             self.register_buffer("frequencies", 2.0 ** torch.arange(f))
 
     m = UpscaleLike()
@@ -200,9 +206,13 @@ def make_module(in_channels, out_channels, upscale_factor, n_frequencies, global
     return m
 
 
-def reference_forward(self, point, res=False, gather=None):
+MUTANTS = ("cat_skip_then_pe", "cos_before_sin")
+
+
+def reference_forward(self, point, res=False, gather=None, mut=None):
     """UpscaleModule.forward / UpscaleResModule.forward (res) of the reference restated; `gather(src, indptr)` is gather_csr
-    (default: repeat_interleave, which also runs on the CPU)"""
+    (default: repeat_interleave, which also runs on the CPU).  `mut` switches one deliberate mistake on."""
+    assert mut in (None,) + MUTANTS
     import torch
 
     s = self.upscale_factor
@@ -218,7 +228,8 @@ def reference_forward(self, point, res=False, gather=None):
     delta_x = 0.5 * point.grid_size * torch.tanh(delta_x)
     x = skip_x + delta_x if self.enable_absolute_pe else delta_x
     fx = torch.flatten(self.frequencies[None, :, None] * x[:, None, :], -2, -1)
-    delta_f = self.delta_f(torch.cat([torch.sin(fx), torch.cos(fx), skip_f], dim=-1))
+    pe = [torch.cos(fx), torch.sin(fx)] if mut == "cos_before_sin" else [torch.sin(fx), torch.cos(fx)]
+    delta_f = self.delta_f(torch.cat([skip_f] + pe if mut == "cat_skip_then_pe" else pe + [skip_f], dim=-1))
     point.coord = skip_x + delta_x
     point.feat = self.skip(skip_f) + self.drop_path(delta_f)
     point.offset = point.offset * s
