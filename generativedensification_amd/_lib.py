@@ -184,6 +184,14 @@ class GdrAttnGatherArgs(C.Structure):   # include/gdr.h gdr_attn_gather_args
                 ("reserved2", C.c_float)]
 
 
+GDR_ATTN_TILED_MAX_SEQLEN, GDR_ATTN_TILED_HEAD_DIM = 16384, 64
+
+
+class GdrAttnTiledArgs(C.Structure):   # include/gdr.h gdr_attn_tiled_args
+    _fields_ = [("B", C.c_int32), ("L", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("dtype", C.c_int32),
+                ("reserved", C.c_int32), ("scale", C.c_float), ("reserved2", C.c_float)]
+
+
 GDR_PF_MAX_VIEWS, GDR_PF_MAX_CHANNELS, GDR_PF_MAX_SIDE, GDR_PF_MAX_POINTS = 16, 4096, 16384, (1 << 31) - 1
 
 
@@ -360,6 +368,10 @@ _PROTOS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gdr_attn_gather_forward": (C.c_int, [C.POINTER(GdrAttnGatherArgs)] + [C.c_void_p] * 8),
     "gdr_attn_gather_backward": (C.c_int, [C.POINTER(GdrAttnGatherArgs)] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 3),
+    "gdr_attn_tiled_scratch_bytes": (C.c_size_t, [C.POINTER(GdrAttnTiledArgs)]),
+    "gdr_attn_tiled_forward": (C.c_int, [C.POINTER(GdrAttnTiledArgs)] + [C.c_void_p, C.POINTER(C.c_int64)] * 3 + [C.c_void_p] * 4),
+    "gdr_attn_tiled_backward": (C.c_int, [C.POINTER(GdrAttnTiledArgs)] + [C.c_void_p, C.POINTER(C.c_int64)] * 4 + [C.c_void_p] * 3 +
+                                [C.c_void_p, C.POINTER(C.c_int64)] * 3 + [C.c_void_p] * 2),
     "gdr_serial_encode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                     C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "gdr_serial_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -703,6 +703,39 @@ int gdr_attn_gather_backward(const gdr_attn_gather_args* a, const void* dout, co
                              const int64_t* inverse, const int32_t* cu_seqlens, const void* out, int32_t out_dtype,
                              const float* lse, void* dqkv, void* stream);
 
+/* ---- tiled MFMA attention for fixed-length batches of long sequences (csrc/attn_tiled.hip; added in v17, backward-compatible)
+ * What a ViT image encoder runs per layer (timm Attention.forward, 1025 tokens at head dimension 64): per image b and head h,
+ * O = softmax(scale Q K^T) V over the key axis, lse_i = log sum_j exp(scale Q_i . K_j).  q, k, v: (B, L, H, D) fp16 or bf16,
+ * each through its own four element strides (batch, token, head, channel); the channel stride must be 1 and every row 16-byte
+ * aligned (a 16-byte aligned base, the other strides multiples of 8), so the three slices of one packed (B, L, 3, H, D)
+ * tensor are read in place.  out: (B, L, H, D) dense in the input dtype, 16-byte aligned; lse: (B, H, L) dense f32.
+ * out_lo: NULL (no backward will follow), or a second buffer like out that receives what out's rounding dropped of the f32
+ * result, rounded to the same dtype: out + out_lo carries 16 (bf16) or 22 (fp16) bits of it.
+ * backward: dout through its four strides under the same rule; out, out_lo and lse as forward wrote them (out_lo NULL: delta
+ * from out alone, whose rounding then shows in dq and dk wherever K or Q has a mean); dq, dk, dv written through
+ * their strides (the three slices of one packed gradient, say); scratch: gdr_attn_tiled_scratch_bytes(a) bytes, 4-byte
+ * aligned (delta_i = sum_d dO_id (O_id + Olo_id)).  Scores, softmax statistics and every accumulation are f32; P and dS are rounded to the
+ * 16-bit dtype only as MFMA operands.  Nothing outside [0, B) x [0, L) of any operand is read or written.
+ * Envelope: D == 64, GDR_F16 / GDR_BF16, 1 <= L <= GDR_ATTN_TILED_MAX_SEQLEN, B and H >= 1, B * H * L < 2^31, a finite scale;
+ * anything else is refused (GDR_ERR_INVALID_ARG, gdr_last_error names the argument) before any launch.  Forward: 1 launch;
+ * backward: 3 (delta, the key-stationary dK / dV kernel, the query-stationary dQ kernel).  No atomics and no hand-off between
+ * workgroups: two runs are bitwise equal.  No host synchronisation. */
+#define GDR_ATTN_TILED_MAX_SEQLEN 16384
+typedef struct gdr_attn_tiled_args {
+    int32_t B, L, H, D;
+    int32_t dtype, reserved;         /* GDR_F16 / GDR_BF16 */
+    float scale, reserved2;          /* softmax scale (the caller resolves the default D^-0.5) */
+} gdr_attn_tiled_args;
+size_t gdr_attn_tiled_scratch_bytes(const gdr_attn_tiled_args* a);   /* 0: the arguments are refused (gdr_last_error) */
+int gdr_attn_tiled_forward(const gdr_attn_tiled_args* a, const void* q, const int64_t* q_strides, const void* k,
+                           const int64_t* k_strides, const void* v, const int64_t* v_strides, void* out, void* out_lo,
+                           float* lse, void* stream);
+int gdr_attn_tiled_backward(const gdr_attn_tiled_args* a, const void* dout, const int64_t* dout_strides, const void* q,
+                            const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                            const int64_t* v_strides, const void* out, const void* out_lo, const float* lse, void* dq,
+                            const int64_t* dq_strides, void* dk, const int64_t* dk_strides, void* dv, const int64_t* dv_strides,
+                            void* scratch, void* stream);
+
 /* ---- point serialization for the point decoder (csrc/serialize.hip; added in v17, backward-compatible) ------------------
  * What the reference's Point.serialization and SerializedAttention.get_padding_and_inverse compute with tensor ops: the
  * space-filling-curve code of every point's grid cell under up to GDR_SERIAL_MAX_ORDERS orders, the stable argsort of each
